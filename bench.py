@@ -2,10 +2,12 @@
 """Headline benchmark of the PRIFIT hot path on MI355X (contract: see the task statement).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--cloud cube|blobs|surface]
-                    [--embedding clustered|untrained|clustered25|retry40] [--no-extra]
+                    [--embedding clustered|untrained|clustered25|retry40] [--full [--no-extra]] [--dump-outputs DIR]
 
 One "step" = one training iteration of the hot path over one batch of B=24 synthetic 2048-point
-clouds per GPU: zero_grad, forward, loss, backward, gradient all-reduce (N>1, RCCL), Adam step.
+clouds per GPU: zero_grad, forward, loss, backward, gradient all-reduce (N>1, RCCL), Adam step.  Every step starts from the
+same seeded parameters and optimizer state (start_state), so that every step does the same work on the same inputs and two
+runs with the same arguments compute the same outputs (to rounding).
   c2: PointNet++-MSG part-seg, segmentation loss only          (BASELINE.json configs[1])
   c3: c2's network + mean-shift (10 it, <=25 clusters) + ellipsoid fit + convex loss (configs[2],
       the configuration the metric is quoted on) -- the self-supervised step of
@@ -18,10 +20,16 @@ shape (`--embedding clustered`, synth.part_embedding_offset: ~8 clusters per sha
 README.md:62).  The seeded untrained network ALONE collapses to ONE cluster per shape: membership is identically 1, the loss
 does not depend on the embedding and the gradient into the whole backbone is exactly zero -- that condition is
 kept as `extra.untrained_embedding`, never `value`.  After the timed region the line asserts that the first backbone layer
-received a gradient (config.backbone_grad_ratio = |grad W| / |W| >= 1e-6; the one-cluster condition gives exactly 0).  At N = 1 the c3 line also carries `extra`: the
-same step on surface clouds, at K = 25, with a retry in every step, the untrained condition, and short c2 / c5 runs --
-shapes/s, clusters per shape, speculation fallbacks and the fit-path kernel rows of each.  `--cloud` / `--embedding` make one
-of them THE measured condition (then named in config).
+received a gradient (config.backbone_grad_ratio = |grad W| / |W| >= 1e-6; the one-cluster condition gives exactly 0).
+
+A plain run sets up, warms up, times K steps and prints the line: no HIP-event spans, no untimed steps after the timed region.
+`--full` adds what the headline does not need: per-kernel rows and rooflines (`kernels`, `roofline`, `roofline_grouping`, from
+event spans on the timed steps), host enqueue time, `launches_per_step`, the CPU baseline (`cpu_baseline`), and at N = 1 the
+c3 line's `extra`: the same step on surface clouds, at K = 25, with a retry in every step, the untrained condition, short
+c2 / c5 runs -- shapes/s, clusters per shape, speculation fallbacks and the fit-path kernel rows of each -- and the
+16-bit-products experiment.  `--cloud` / `--embedding` make one of them THE measured condition (then named in config).
+`--dump-outputs DIR` writes what the last timed step computed (loss, network outputs, parameters and gradients after the
+update: step_outputs) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no RANK in the environment: this process only LAUNCHES -- it starts N copies of
 itself, one per GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set (prifit_amd/launch.py), before anything
@@ -74,6 +82,7 @@ DEFAULT_EMBEDDING = {"c2": "untrained", "c3": "clustered", "c5": "clustered"}
 # |grad W| / |W| of the FIRST backbone layer after the last timed step, asserted outside the timed region.  Measured (round 6):
 # c3 clustered 4e-5 (first steps) .. 5e-4 (after 25 Adam steps), surface clouds 6e-5, c5 7e-5, c2 8e-3, K = 25 4e-6; the one-cluster
 # condition gives EXACTLY 0 on the HIP path and <= 1e-8 (rounding noise) in the oracle -- the bar sits between the two.
+# (Every step now starts from the seeded state, start_state: measured c3 1.2e-4, c5 2.0e-5, c2 4.0e-2, K = 25 4.0e-6.)
 MIN_BACKBONE_GRAD_RATIO = 1e-6
 METRIC = {"c2": "shapes/sec (fwd+bwd) B=24x2048 pts, PointNet++-MSG seg loss only",
           "c3": "shapes/sec (fwd+bwd) B=24x2048 pts, PointNet++-MSG+ellipsoid fit",
@@ -325,7 +334,10 @@ def run_rank(args):
     ctx = {"world": world, "rank": rank, "local": local, "device": device, "use_dist": use_dist, "backend": backend,
            "share": share}
     cloud = args.cloud or DEFAULT_CLOUD[args.workload]
-    head = measure(args, ctx, cloud, args.embedding, args.steps, args.warmup, full=True, split=args.ms_split)
+    head = measure(args, ctx, cloud, args.embedding, args.steps, args.warmup, full=True, split=args.ms_split,
+                   lean=not args.full, dump=bool(args.dump_outputs) and rank == 0)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(head.pop("outputs"), args.dump_outputs)
 
     report = None
     if use_dist:
@@ -352,8 +364,8 @@ def run_rank(args):
             line["experiment"] = SPLIT_NOTE
         if backend != "nccl" and use_dist:
             line["rehearsal"] = "backend=%s%s: NOT a reportable number" % (backend, ", ranks share GPUs" if share else "")
-    # the same step under other conditions, beside the headline (single GPU, c3, default condition only)
-    if world == 1 and args.workload == "c3" and not args.no_extra and args.default_condition and args.ms_split == "0":
+    # the same step under other conditions, beside the headline (--full, single GPU, c3, default condition only)
+    if args.full and world == 1 and args.workload == "c3" and not args.no_extra and args.default_condition and args.ms_split == "0":
         # (the headline is measured and stays: an exception in a side measurement is recorded in its entry, not raised)
         extra = {}
         short = max(10, min(args.steps, 30))
@@ -392,13 +404,13 @@ def run_rank(args):
                                      "speculation_fallbacks": v.get("speculation_fallbacks"), "error": v.get("error")}
                                  for k, v in extra.items() if k != "split_mean_shift_products_experiment"}
     if rank == 0:
-        if world == 1 and os.environ.get("PRIFIT_BENCH_COUNT_LAUNCHES", "1") != "0":
+        if args.full and world == 1 and os.environ.get("PRIFIT_BENCH_COUNT_LAUNCHES", "1") != "0":
             try:   # after every timed measurement of this process
                 line["launches_per_step"] = count_launches(head["_step"])
             except Exception as e:   # noqa: BLE001
                 line["launches_per_step"] = None
                 line["launches_per_step_error"] = "%s: %s" % (type(e).__name__, e)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_baseline_shapes,
                                                     passes=5 if args.cpu_baseline_shapes <= 8 else 2)
@@ -420,23 +432,89 @@ FIT_FAMILIES = ("chord_sym", "chord_sym_mask", "kth_smallest", "ms_first_fwd", "
                 "ellipsoid_fit", "sdf", "sample_nn", "sample_nn_bwd")
 
 
-def measure(args, ctx, cloud, embedding, steps, warmup, full, split="0", workload=None):
+def measure(args, ctx, cloud, embedding, steps, warmup, full, split="0", workload=None, lean=False, dump=False):
     """Build the network and the inputs of one condition, run `warmup` untimed + `steps` timed training steps bracketed by
     barrier + synchronize, and return the raw measurements.  full: the headline's extras (enqueue time, all ranks' MAX).
     split: the LABELLED EXPERIMENT of csrc/meanshift_split.hip for this measurement ("0" = the fp32 product path).
-    workload: another workload than args.workload (the short c2 / c5 side runs of the c3 line)."""
+    workload: another workload than args.workload (the short c2 / c5 side runs of the c3 line).
+    lean: the timed steps and nothing else (a run without --full): no HIP-event spans, no untimed steps after the timed
+    region; `full` is then ignored.  dump: res["outputs"], what the last timed step computed (step_outputs)."""
     from prifit_amd import fit_ops
     fit_ops.MS_SPLIT = split
     if workload is not None and workload != args.workload:
         args = argparse.Namespace(**dict(vars(args), workload=workload))
     try:
-        return _measure(args, ctx, cloud, embedding, steps, warmup, full)
+        return _measure(args, ctx, cloud, embedding, steps, warmup, full, lean, dump)
     finally:
         fit_ops.MS_SPLIT = "0"
         gc.enable()   # (_measure switches the cyclic collector off around its timed region)
 
 
-def _measure(args, ctx, cloud, embedding, steps, warmup, full):
+def step_outputs(net, out, loss):
+    """What the caller of the timed step receives from its last call, copied to the host as float32 (the loss: float64): the
+    loss, the network's outputs of that step (`out`: its forward's tuple; c2: the segmentation output alone) and the
+    parameters and their gradients after the step's Adam update, each flattened in `net.parameters()` order."""
+    import torch
+    d = {"loss": loss.detach().double().reshape(1), "seg_log_probs": out[0]}
+    if len(out) > 7:   # the fit path (c3 / c5): convex and chamfer losses, clusters per shape, the embedding it clustered
+        d.update(convex_loss=out[3], chamfer_loss=out[4], clusters_per_shape=out[6].count, embedding=out[7])
+    params = list(net.parameters())
+    d["parameters"] = torch.cat([p.detach().reshape(-1) for p in params])
+    d["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    return {k: v.detach().cpu().numpy().astype("float64" if k == "loss" else "float32") for k, v in d.items()}
+
+
+DUMP_MAX_ELEMENTS = 1 << 22     # per array (16 MiB of float32): a larger output is written as a fixed, seeded sample of its elements
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: one DIR/<name>.npy per array of step_outputs.  An array of more than DUMP_MAX_ELEMENTS elements is
+    flattened and sampled at the same sorted seeded positions in every run (the sample depends on its size alone)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in sorted(outputs.items()):
+        a = np.ascontiguousarray(a)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit("bench.py --dump-outputs: more than %d bytes at %s" % (DUMP_MAX_BYTES, name))
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def start_state(net, opt):
+    """Every step -- warm-up and timed alike -- is one training step from the same seeded state: the returned function puts the
+    parameters and the optimizer state (moments, step counts) back to what they are now, in place (FlatAdam: five device
+    copies; the allocator's blocks and the optimizer's address table stay as they are).  The step's work is unchanged, and its
+    inputs, and so what it computes, are the same in every step of every run: without it the float-atomic rounding noise of
+    one step reaches the next one's parameters through Adam and the clustering, and grows from step to step until two runs
+    with the same arguments disagree in every output."""
+    import torch
+    beta = getattr(net, "beta", None)   # (the entropy-loss weight the model decays per forward; not in the measured loss)
+    if hasattr(opt, "flat"):
+        pairs = [(t, t.clone()) for t in (opt.flat, opt.exp_avg, opt.exp_avg_sq) + tuple(opt._steps)]
+        cur = opt._cur
+
+        def restart():
+            for t, t0 in pairs:
+                t.copy_(t0)
+            opt._cur = cur
+            net.beta = beta
+    else:   # torch's Adam (the A/B arm): no state before its first step
+        params = [p for p in net.parameters()]
+        saved = [p.detach().clone() for p in params]
+
+        def restart():
+            with torch.no_grad():
+                torch._foreach_copy_(params, saved)
+            opt.state.clear()
+            net.beta = beta
+    return restart
+
+
+def _measure(args, ctx, cloud, embedding, steps, warmup, full, lean=False, dump=False):
     import torch
     import torch.distributed as dist
     from prifit_amd import profiler, synth
@@ -453,6 +531,7 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
         opt = FlatAdam(net.parameters(), lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4)
     else:
         opt = torch.optim.Adam(net.parameters(), lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, fused=True)
+    restart = start_state(net, opt)
     data = make_inputs(args.workload, rank, device, cloud)
     crit = M.get_loss() if M is not None else None
     runner = SpeculativeRunner(net)
@@ -506,16 +585,21 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
             out = net(data["xyz"], data["cls"], fps_start=sampled["cur"], **fit_kw)
         loss = out[3].mean()
         last["count"] = out[6].count      # clusters per shape (device tensor; read after the timed region)
+        if dump:
+            last["out"] = out
         sample_next()
         loss.backward()
         return loss
 
     def step():
+        restart()
         if ahead_on:
             sampled["cur"] = sampled["next"] if sampled["next"] is not None else starts
         bucket.zero()
         if args.workload == "c2":
             seg = net(data["xyz"], data["cls"], fps_start=sampled["cur"])[0]
+            if dump:
+                last["out"] = (seg,)
             sample_next()
             loss = crit(seg.reshape(-1, NUM_PARTS), data["target"].view(-1), None)
             loss.backward()
@@ -565,6 +649,9 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
     gc.disable()
     cal = None
     for _ in range(ncal):
+        if lean:   # (the same untimed steps, without the event spans)
+            step()
+            continue
         profiler.reset()
         profiler.enable("*")
         step()
@@ -584,7 +671,9 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
         torch.cuda.synchronize()
         graph_note = ("backbone forward + backward replayed as two HIP graphs (train_step.graph_backbone); the grouping "
                       "launches are inside them: roofline_grouping from the last eager warm-up step")
-    if os.environ.get("PRIFIT_BENCH_EVENTS", "1") == "all":   # diagnosis: every family bracketed (slows the step down)
+    if lean:
+        pass
+    elif os.environ.get("PRIFIT_BENCH_EVENTS", "1") == "all":   # diagnosis: every family bracketed (slows the step down)
         profiler.enable("*")
     elif os.environ.get("PRIFIT_BENCH_EVENTS", "1") != "0":  # 0: diagnosis only (no roofline objects in the line)
         profiler.enable(*[n for n in (dominant,) + GROUPING_FAMILIES if n])
@@ -618,7 +707,7 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
     if use_dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     fams = profiler.collect()
-    if graph_note:   # the launches inside the graphs carry no events: their rows come from the calibration step (one eager step)
+    if graph_note and cal:   # the launches inside the graphs carry no events: their rows come from the calibration step (one eager step)
         for k in GROUPING_FAMILIES:
             if k in cal and k not in fams:
                 n, ms, work = cal[k]
@@ -627,7 +716,11 @@ def _measure(args, ctx, cloud, embedding, steps, warmup, full):
            "fallbacks": runner.fallbacks - fallbacks0, "ahead_on": ahead_on, "grad_ratio": grad_ratio, "grad_param": wname,
            "_step": step,
            "clusters": last["count"].tolist() if "count" in last else None}
-    if full:
+    if dump:   # before any further step changes the parameters
+        res["outputs"] = step_outputs(net, last["out"], loss)
+    if lean:
+        pass
+    elif full:
         # host time to ENQUEUE one step, measured outside the timed region from an empty queue (inside it the launch
         # thread runs ahead until the queue is full and then advances at the GPU's pace, which says nothing)
         # (c3 / c5: the host then BLOCKS until the GPU reaches the clustering verdict of this very step, ~8 ms in -- that wait is
@@ -798,6 +891,24 @@ def headline(args, ctx, r, cloud):
     steps = r["steps"]
     ms_per_step = 1e3 * r["elapsed"] / steps
     value = world * B_PER_GPU * steps / r["elapsed"]
+    line = {
+        "metric": METRIC[args.workload],
+        "value": value, "unit": "shapes/s", "n_gpus": world, "steps": steps, "warmup": r["warmup"],
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": WORKLOADS[args.workload],
+                   "global_batch": world * B_PER_GPU, "points": NPTS, "parallelism": "dp%d" % world,
+                   "cloud": cloud, "embedding": args.embedding if args.workload != "c2" else None,
+                   "clusters_per_shape": (sum(r["clusters"]) / len(r["clusters"])) if r["clusters"] else None,
+                   "backbone_grad_ratio": r["grad_ratio"], "backbone_grad_param": r["grad_param"],
+                   "loss": r["loss"],
+                   "launch": r.get("graph") or "eager",
+                   "fps": ("side stream, one batch ahead: every step launches one batch's sampling (behind its backbone forward) "
+                           "and consumes the previous launch; PRIFIT_SAMPLE_AHEAD=0 runs it in line" if r["ahead_on"] else "in line")},
+        "speculation_fallbacks": r["fallbacks"],
+    }
+    if not args.full:
+        return line
     detail = family_rows(r["fams"], steps)
     roof = None
     if detail:
@@ -822,26 +933,9 @@ def headline(args, ctx, r, cloud):
         n = sum(v["launches_per_step"] for k, v in detail.items() if k.split("[")[0] == "sa_group_linear")
         grouping["own_bytes"]["pmc_gbytes_per_step"] = (pmc * n / 1e9) if (pmc and n) else None
         grouping["own_bytes"]["pmc_source"] = src
-    ks = r["clusters"]
-    line = {
-        "metric": METRIC[args.workload],
-        "value": value, "unit": "shapes/s", "n_gpus": world, "steps": steps, "warmup": r["warmup"],
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": WORKLOADS[args.workload],
-                   "global_batch": world * B_PER_GPU, "points": NPTS, "parallelism": "dp%d" % world,
-                   "cloud": cloud, "embedding": args.embedding if args.workload != "c2" else None,
-                   "clusters_per_shape": (sum(ks) / len(ks)) if ks else None,
-                   "backbone_grad_ratio": r["grad_ratio"], "backbone_grad_param": r["grad_param"],
-                   "loss": r["loss"],
-                   "launch": r.get("graph") or "eager",
-                   "fps": ("side stream, one batch ahead: every step launches one batch's sampling (behind its backbone forward) "
-                           "and consumes the previous launch; PRIFIT_SAMPLE_AHEAD=0 runs it in line" if r["ahead_on"] else "in line")},
-        "roofline": roof, "roofline_grouping": grouping, "kernels": detail, "roofline_model_violations": over,
-        "speculation_fallbacks": r["fallbacks"],
-        "host_enqueue_ms_per_step": 1e3 * r["t_host"],
-        "host_verdict_wait_ms_per_step": 1e3 * r.get("t_host_wait", 0.0),
-    }
+    line.update({"roofline": roof, "roofline_grouping": grouping, "kernels": detail, "roofline_model_violations": over,
+                 "host_enqueue_ms_per_step": 1e3 * r["t_host"],
+                 "host_verdict_wait_ms_per_step": 1e3 * r.get("t_host_wait", 0.0)})
     return line
 
 
@@ -850,7 +944,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: 10 warm-up steps bring the clocks and the caching allocator to steady state (with 3 the first timed
     # steps still run ~10 % slow); 200 timed steps = ~5 s of GPU work (a sampled GPU-busy monitor sees it beside the ~15 s
-    # CPU-baseline leg; 50 steps measure the same rate to 0.3 %)
+    # CPU-baseline leg of --full; 50 steps measure the same rate to 0.3 %)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default=os.environ.get("PRIFIT_WORKLOAD", "c3"), choices=sorted(WORKLOADS))
@@ -862,6 +956,11 @@ def main():
                     help="default: clustered for c3 / c5 (~8 clusters per shape: real gradients into the backbone), n/a for c2")
     ap.add_argument("--no-extra", action="store_true", help="skip the training-like conditions reported under `extra`")
     ap.add_argument("--graph", action="store_true", help="replay the backbone forward + backward as HIP graphs (static shapes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel rows and rooflines (HIP-event spans), "
+                         "host enqueue time, launches per step, the `extra` conditions and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--ms-split", default="0", choices=("0", "bf16x3", "bf16x6", "fp16x3"),
                     help="LABELLED EXPERIMENT: mean-shift forward products on the 16-bit matrix pipe, error-compensated; the line's "
                          "dtype says so and it is never the reported fp32 number")

@@ -10,6 +10,7 @@ import subprocess
 import sys
 import tempfile
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,8 +32,16 @@ def test_bench_launch_paths_agree(hiplib):
     from prifit_amd import launch
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     bench = os.path.join(ROOT, "bench.py")
-    plain = _line([sys.executable, bench, "--gpus", "1"] + ARGS, base)
-    assert plain["n_gpus"] == 1 and plain["config"]["global_batch"] == 24
+    with tempfile.TemporaryDirectory() as d:
+        plain = _line([sys.executable, bench, "--gpus", "1", "--dump-outputs", d] + ARGS, base)
+        # --dump-outputs: what the last timed step computed, as float32 / float64 arrays
+        out = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert plain["n_gpus"] == 1 and plain["config"]["global_batch"] == 24 and plain["steps"] == 2
+    assert "kernels" not in plain and "launches_per_step" not in plain     # per-kernel rows and launch counts: --full only
+    assert {"loss", "seg_log_probs", "parameters", "gradients"} <= set(out)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["loss"][0] == plain["config"]["loss"] and out["seg_log_probs"].shape == (24, 2048, 50)
+    assert out["parameters"].shape == out["gradients"].shape and np.isfinite(out["gradients"]).all()
     one = _line([sys.executable, bench, "--gpus", "1"] + ARGS, launch.rank_env(0, 1, launch.free_port(), base))
     assert one["n_gpus"] == 1
     # the N > 1 line proves itself: world size and backend from the communicator, who ran where
@@ -99,7 +108,7 @@ def test_labelled_experiment_line_says_what_it_is(hiplib):
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     base["PRIFIT_BENCH_EVENTS"] = "all"     # every kernel family in `kernels` (by default only the dominant one and the grouping launches)
     bench = os.path.join(ROOT, "bench.py")
-    args = ["--steps", "2", "--warmup", "2", "--workload", "c3", "--no-cpu-baseline", "--no-extra"]
+    args = ["--steps", "2", "--warmup", "2", "--workload", "c3", "--full", "--no-cpu-baseline", "--no-extra"]
     exp = _line([sys.executable, bench] + args + ["--ms-split", "fp16x3"], base)
     assert exp["dtype"].startswith("f32 (mean-shift forward products fp16x3 emulated") and "experiment" in exp
     assert "extra" not in exp and any(k.startswith("ms_split_fwd[fp16x3]") for k in exp["kernels"])

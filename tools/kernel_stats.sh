@@ -2,10 +2,10 @@
 # usage (GPU box): tools/kernel_stats.sh <tag> <workload> [pattern]  -- rocprofv3 kernel statistics of one bench run into
 # gpurun_out/<tag>/<workload>_kernel_stats.csv, and the rows matching `pattern` (default: the 30 largest) per step
 tag=$1; w=$2; pat=${3:-}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$w -o $w -- python3 $root/bench.py --workload $w --no-cpu-baseline --no-extra --steps 40 --warmup 3 > $out/prof_$w.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$w -o $w -- python3 $root/bench.py --full --workload $w --no-cpu-baseline --no-extra --steps 40 --warmup 3 > $out/prof_$w.log 2>&1 )
 cp $out/prof_$w/*kernel_stats.csv $out/${w}_kernel_stats.csv 2>/dev/null || cp $out/prof_$w/*/*kernel_stats.csv $out/${w}_kernel_stats.csv
 rm -rf $out/prof_$w
 python3 - $out/${w}_kernel_stats.csv "$pat" <<'PY'

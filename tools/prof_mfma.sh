@@ -3,7 +3,7 @@
 # One rocprofv3 --pmc pass (SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE) with the kernel trace over a short bench run;
 # tools/pmc_mfma.py turns it into matrix-core utilisation per kernel family -> gpurun_out/mfma_<tag>/mfma.json
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/mfma_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # SQ counter passes over the fused mean-shift micro-benchmark (tools/msfused_bench.py): where do the waves spend their
 # cycles (parked on s_waitcnt / barriers, issue stalls, active) -> gpurun_out/msf_<tag>/
 tag=$1
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/msf_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

@@ -4,7 +4,7 @@
 # tools/pmc_traffic.py turns the per-dispatch counters into HBM bytes per launch for every GEMM family
 # -> gpurun_out/pmc_<tag>/traffic.json (copy to profiles/ to have bench.py report roofline.traffic).
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/pmc_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/prof_sq_bench.sh <tag> [bench args…]   SQ counter passes over a short bench run
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/sq_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp

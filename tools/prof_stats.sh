@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/prof_stats.sh <tag> [bench args…]  -> gpurun_out/prof_<tag>/, prints top kernels
 tag=$1; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $root/gpurun_out/prof_$tag -o $tag -- python3 $root/bench.py --no-cpu-baseline --steps 5 --warmup 3 "$@" > $root/gpurun_out/prof_$tag.log 2>&1
 cd $root

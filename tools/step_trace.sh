@@ -2,7 +2,7 @@
 # usage (GPU box): tools/step_trace.sh <tag> <workload>  -- the kernel sequence of ONE timed step (between two optimizer launches),
 # start offset / duration / name, into gpurun_out/<tag>/<workload>_step_trace.txt
 tag=$1; w=$2
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --output-format csv -d $out/trace_$w -o $w -- python3 $root/bench.py --workload $w --no-cpu-baseline --no-extra --steps 6 --warmup 3 > $out/trace_$w.log 2>&1 )
