@@ -665,14 +665,19 @@ __global__ __launch_bounds__(512) void ms_rows_chain_kernel(RowsArgs a, QueueArg
         float4 acc[NV], xb[PD + 1][NV];
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-        // (buffer loads: a scalar offset per pass + ONE loop-invariant lane offset, keys beyond N read as zeros without a branch
-        // -- a branch around a load makes the compiler wait for the loads before it, and the passes in flight are gone)
+        // (buffer loads, the whole offset in the lane offset: keys beyond N fail the bounds check -- read as zeros, no access --
+        // without a branch; a branch around a load makes the compiler wait for the loads before it, and the passes in flight
+        // are gone.  The pass base used to go into the scalar offset, which the bounds check is not documented to cover
+        // (meanshift_fused.hip keeps it out of the check for the same reason): the passes beyond N, up to (npass + PD) x 64 - N
+        // rows past the shape's slice of X, then rested on it, and a NaN or Inf there reaches acc through fma(0, x, acc).  On
+        // the MI355X, with X inside NaN guards, that form read zeros too (tests/test_gpu_meanshift_guards.py); this one does
+        // not depend on it, for one VALU add per pass and no measurable time.)
         const int off0 = (ks * D + 4 * o) * 4;
         auto load = [&](float4 (&x)[NV], int key) {
-            const int soff = (key - ks) * D * 4;
+            const int voff = off0 + (key - ks) * D * 4;
 #pragma unroll
             for (int v = 0; v < NV; ++v)
-                x[v] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off0 + 128 * v, soff, 0));
+                x[v] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, voff + 128 * v, 0, 0));
         };
         // (sched_barrier: the loads leave in pass order -- the wait for a pass is "all but the N newest", and a pass whose loads
         // were issued last would make that wait a wait for everything)
@@ -682,7 +687,7 @@ __global__ __launch_bounds__(512) void ms_rows_chain_kernel(RowsArgs a, QueueArg
 #pragma unroll
             for (int i = 0; i <= PD; ++i) {
                 const int key = (p + i) * KPP + ks;
-                load(xb[(i + PD) % (PD + 1)], key + PD * KPP);          // (beyond N: zeros, no access)
+                load(xb[(i + PD) % (PD + 1)], key + PD * KPP);          // (beyond N: out of bounds -- zeros, no access)
                 __builtin_amdgcn_sched_barrier(0);
                 const float4 (&xc)[NV] = xb[i];
                 // (two-wide packed FMAs, v_pk_fma_f32: half the instructions; measured the same 13.7 us per iteration as scalar

@@ -1,0 +1,77 @@
+"""The guard-band helper of the kernel tests (tests/guard_common.py), on the CPU."""
+import math
+
+import pytest
+import torch
+
+from guard_common import (ALIGN, SENTINEL, assert_guards_intact, guarded, guarded_like, padded_stream, poison_bits, x_tail)
+
+
+def test_guarded_view_alignment_contiguity_and_poison():
+    for shape, lead, tail in (((3, 300, 128), 5, x_tail(128)), ((7,), 0, 1), ((2, 33, 32), 1000, 17)):
+        view, base = guarded(shape, lead, tail, device="cpu")
+        assert view.shape == shape and view.dtype == torch.float32 and view.is_contiguous()
+        assert view.data_ptr() % ALIGN == 0
+        assert view.contiguous().data_ptr() == view.data_ptr()
+        s = view.storage_offset() - base.storage_offset()
+        assert s >= lead and base.numel() - s - view.numel() >= tail
+        assert torch.isnan(base).all()                      # the view too, until filled
+        view.fill_(1.0)
+        assert torch.isnan(base[:s]).all() and torch.isnan(base[s + view.numel():]).all()
+        assert int((base == 1.0).sum()) == math.prod(shape)
+    assert x_tail(128) == (1 << 20) // 4 and x_tail(1024) == 512 * 1024
+
+
+def test_guarded_like_and_sentinel_bits():
+    t = torch.arange(12, dtype=torch.float32).view(3, 4)
+    view, base = guarded_like(t, 4, 4, poison=SENTINEL)
+    assert torch.equal(view, t)
+    assert_guards_intact(base, view)
+    assert poison_bits(SENTINEL) == SENTINEL and poison_bits(0xffffffff) == -1
+    assert poison_bits(float("nan")) == 0x7fc00000 and poison_bits(1.0) == 0x3f800000
+
+
+def test_padded_stream_layout():
+    B, N, ld, stride = 3, 5, 12, 5 * 12 + 8
+    st, base = padded_stream(B, N, ld, stride, poison=SENTINEL, device="cpu")
+    assert st.shape == (B, N, ld) and st.stride() == (stride, ld, 1) and st.data_ptr() % ALIGN == 0
+    s = st.storage_offset() - base.storage_offset()
+    assert s >= stride and base.numel() - s - B * stride >= stride
+    st[..., :N] = 2.0
+    bits = base.view(torch.int32)
+    assert int((base == 2.0).sum()) == B * N * N
+    assert int((bits == SENTINEL).sum()) == base.numel() - B * N * N
+    for b in range(B):                                      # element (b, i, j) at b * stride + i * ld + j
+        for i in range(N):
+            row = base[s + b * stride + i * ld:s + b * stride + (i + 1) * ld]
+            assert (row[:N] == 2.0).all() and (row[N:].view(torch.int32) == SENTINEL).all()
+        gap = base[s + b * stride + N * ld:s + (b + 1) * stride]
+        assert gap.numel() == stride - N * ld and (gap.view(torch.int32) == SENTINEL).all()
+    assert_guards_intact(base, st[..., :N])
+    with pytest.raises(AssertionError):
+        padded_stream(B, N, N - 1, stride, device="cpu")
+
+
+@pytest.mark.parametrize("where", ["lead", "tail", "pad", "gap"])
+def test_assert_guards_intact_catches_one_word(where):
+    if where in ("lead", "tail"):
+        view, base = guarded((4, 8), 16, 16, poison=SENTINEL, device="cpu")
+        view.zero_()
+        s = view.storage_offset()
+        at = s - 1 if where == "lead" else s + view.numel()
+        inner = view
+    else:
+        N, ld, stride = 4, 8, 4 * 8 + 4
+        st, base = padded_stream(2, N, ld, stride, poison=SENTINEL, device="cpu")
+        inner = st[..., :N]
+        inner.zero_()
+        s = st.storage_offset()
+        at = s + 2 * ld + N + 1 if where == "pad" else s + N * ld + 2
+    assert_guards_intact(base, inner)
+    base.view(torch.int32)[at] = SENTINEL ^ 1              # still a NaN, one bit off
+    with pytest.raises(AssertionError, match="1 guard word"):
+        assert_guards_intact(base, inner)
+    base.view(torch.int32)[at] = SENTINEL
+    assert_guards_intact(base, inner)
+    inner[(0,) * inner.dim()] = float("nan")                 # the view itself is not a guard
+    assert_guards_intact(base, inner)
