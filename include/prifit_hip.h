@@ -32,38 +32,10 @@ extern "C" {
 #define PRIFIT_EINVAL (-1)   /* bad argument (shape / alignment / unsupported size) */
 #define PRIFIT_ELAUNCH (-2)  /* hipGetLastError() != hipSuccess after the launch   */
 
-/* BatchNorm tails (round 6).  A kernel that produces the per-column sums of a BatchNorm layer can also FINALIZE them: pass one of
- * these descriptors (host structs, read at launch) instead of a statistics-slab pointer and the launch leaves the layer's
- * coefficients in `out` -- the separate prifit_bn_finalize / prifit_bn_bwd_finalize launch (and the slab) disappear.
- *   acc     [prifit_bn_tail_replicas()][2][C] doubles, ZERO on entry (left zero);  ticket  one int32, ZERO on entry (left zero)
- * prifit_bn_fwd: train-mode nn.BatchNorm of models/pointnet_util.py:195-197 / :250-252 / :310-313 -- out [4][C] = scale
- *   (gamma * invstd), shift (beta - mean * scale), mean, invstd; running statistics updated with `momentum` (unbiased variance)
- *   when the pointers are given; count = rows behind the sums.
- * prifit_bn_bwd: its autograd -- out [5][C] = dgamma, dbeta and the coefficients (a, b, d) of dY = a Gm + b Y + d.
- * A NULL descriptor (or acc == NULL) keeps the slab form of the entry point. */
-int prifit_bn_tail_replicas(void);
-
-typedef struct prifit_bn_fwd {
-    double *acc;
-    int32_t *ticket;
-    const float *gamma, *beta;
-    float *running_mean, *running_var;
-    float *out;
-    double count;
-    float eps, momentum;
-} prifit_bn_fwd;
-
-typedef struct prifit_bn_bwd {
-    double *acc;
-    int32_t *ticket;
-    const float *scale, *mean, *invstd;
-    float *out;
-    double count;
-    int training;
-} prifit_bn_bwd;
-
-/* Library identification: returns 10000*major + 100*minor + patch; *arch (may be NULL) receives a
- * static string naming the code object target ("gfx950"). */
+/* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
+ * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
+ * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
+#define PRIFIT_ABI_VERSION 200
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -187,8 +159,7 @@ int prifit_gemm_f32(int layout, int M, int N, int K, const float *A, long long l
                     const float *a_shift, const float *b_scale, const float *b_shift,
                     const float *bias, long long bias_batch_stride, float *col_stats, int epilogue,
                     const float *epi_batch_scalar, const float *epi_aux, long long ld_aux,
-                    long long stride_aux, const float *epi_row_add, float *a_rowsum, int accumulate,
-                    const prifit_bn_fwd *bn, void *stream);
+                    long long stride_aux, const float *epi_row_add, float *a_rowsum, int accumulate, void *stream);
 
 /* Chord-distance matrix of a point set with itself (src/mean_shift.py:154 bandwidth statistic, :185 non-maximum
  * suppression): C[z] = 2 - 2 A[z] A[z]^T for unit rows, [n, n] per batch item; n % 128 == 0, K % 32 == 0, 16-byte rows.
@@ -219,7 +190,7 @@ int prifit_gram_sym_f32(const float *A, long long lda, long long strideA, float 
  * only: 201 MB less written for that layer at B = 24 x 2048). */
 int prifit_gemm_pool_f32(int M, int N, int K, const float *A, long long lda, const float *W, long long ldb, float *Y,
                          long long ldc, const float *a_scale, const float *a_shift, const float *bias, float *col_stats,
-                         float *cand, const prifit_bn_fwd *bn, void *stream);
+                         float *cand, void *stream);
 int prifit_gemm_pool_supported(int M, int N, int K);
 
 /* Weights-stationary streaming variant for the tall-and-skinny (HBM-bound) layers of the shared MLPs: layout
@@ -229,7 +200,7 @@ int prifit_gemm_pool_supported(int M, int N, int K);
  * [prifit_gemm_stream_slabs(M,K)][2][N] or NULL receives one column (sum, sum of squares) slab per workgroup. */
 int prifit_gemm_stream_f32(int layout, int M, int N, int K, const float *A, long long lda, const float *B,
                            long long ldb, float *C, long long ldc, const float *a_scale, const float *a_shift,
-                           const float *bias, float *col_stats, const prifit_bn_fwd *bn, void *stream);
+                           const float *bias, float *col_stats, void *stream);
 int prifit_gemm_stream_supported(int layout, int M, int N, int K);  /* 1 / 0 */
 int prifit_gemm_stream_slabs(int M, int K);                         /* workgroups = statistics slabs */
 
@@ -245,8 +216,7 @@ int prifit_gemm_dual_nn_f32(int M, int N, int K1, int K2, const float *A1, const
  * red_slab [ceil(M / prifit_gemm_stats_tile_m(M, N))][2][N] receiving the (m1, m2) partials described below. */
 int prifit_gemm_dgrad_bnred_f32(int M, int N, int K, const float *dY, long long lda, const float *W, long long ldb,
                                 float *G, long long ldc, const float *Yprev, long long ldy, const float *scale,
-                                const float *shift, const float *mean, const float *invstd, float *red_slab,
-                                const prifit_bn_bwd *bn, void *stream);
+                                const float *shift, const float *mean, const float *invstd, float *red_slab, void *stream);
 /* The winners' terms of a layer max-pooled over the WHOLE cloud (src/dgcnn.py:194-197: x.max(dim=-1) behind conv + GroupNorm +
  * ReLU; one pooling group per sample, K rows, Cout winners), backward in the algebraic form (csrc/pool_alg.hip):
  *   dX[b, arg[b,c], :] += T[b,c] W[c, :]   (rows; channels in ascending order)      dX [Bs K, lddx], NULL: skipped
@@ -273,13 +243,13 @@ int prifit_global_pool_winners_f32(int Bs, int K, int Cout, int Cin, const int32
  * only); rows_per_centre % 64 == 0, M % (n_centres * rows_per_centre) == 0. */
 int prifit_gemm_stream_gather_f32(int M, int N, const int32_t *idx, const float *U, const float *Vc, int n_points, int n_centres,
                                   int rows_per_centre, const float *B, long long ldb, float *C, long long ldc,
-                                  const float *a_scale, const float *a_shift, const float *bias, float *col_stats, const prifit_bn_fwd *bn, void *stream);
+                                  const float *a_scale, const float *a_shift, const float *bias, float *col_stats, void *stream);
 int prifit_gemm_stream_bwd_gather_f32(long long P, int Cout, const float *G, const float *Y, const float *scale,
                                       const float *shift, const float *coef_a, const float *coef_b, const float *coef_d,
                                       const float *W, long long ldw, const int32_t *idx, const float *U, const float *Vc,
                                       int n_points, int n_centres, int rows_per_centre, const float *p_scale,
                                       const float *p_shift, const float *p_mean, const float *p_invstd, float *Gp, long long ldgp,
-                                      float *red_slab, float *dW, long long lddw, float *workspace, const prifit_bn_bwd *bn, void *stream);
+                                      float *red_slab, float *dW, long long lddw, float *workspace, void *stream);
 /* Forward of a max-pooled last layer without re-reading it for the pool (models/pointnet_util.py:199,256):
  * prifit_gemm_stream_f32 (NT, prologue required, M % 32 == 0) that also emits, per 32-row block and column, the largest
  * and smallest stored C and the row of their first occurrence, cand [M/32][4][N]; once the BatchNorm affine (scale,
@@ -290,7 +260,7 @@ int prifit_gemm_stream_bwd_gather_f32(long long P, int Cout, const float *G, con
  * Y when the layer's gradients come from its input (csrc/pool_alg.hip), so that the product need not store Y at all. */
 int prifit_gemm_stream_pool_f32(int M, int N, int K, const float *A, long long lda, const float *B, long long ldb,
                                 float *C, long long ldc, const float *a_scale, const float *a_shift, const float *bias,
-                                float *col_stats, float *cand, const prifit_bn_fwd *bn, void *stream);
+                                float *col_stats, float *cand, void *stream);
 int prifit_pool_from_candidates(const float *cand, const float *scale, const float *shift, int G, int K, int C,
                                 int rows_per_sample, float slope, float *out, long long ldo, int32_t *arg, float *ystar,
                                 void *stream);
@@ -302,8 +272,7 @@ int prifit_pool_from_candidates(const float *cand, const float *scale, const flo
  * prifit_bn_relu_bwd_reduce would otherwise compute by re-reading G (autograd of models/pointnet_util.py:195-199). */
 int prifit_gemm_stream_dgrad_f32(int M, int N, int K, const float *dY, long long lda, const float *W, long long ldb,
                                  float *G, long long ldc, const float *Yprev, long long ldy, const float *scale,
-                                 const float *shift, const float *mean, const float *invstd, float *red_slab,
-                                 const prifit_bn_bwd *bn, void *stream);
+                                 const float *shift, const float *mean, const float *invstd, float *red_slab, void *stream);
 
 /* The max-pooled LAST layer of a per-group MLP (models/pointnet_util.py:199,256), autograd without materialising
  * its dY: with (a, b, d) = prifit_bn_bwd_finalize's coefficients, dY[g,k,c] = T[g,c]*[k == arg[g,c]] + b[c]*Y[g,k,c] + d[c]
@@ -320,7 +289,7 @@ int prifit_gemm_stream_dgrad_pool_f32(int M, int N, int K, const float *Y, long 
                                       float *G, long long ldc, const float *bias_dW, const int32_t *pool_arg,
                                       const float *pool_T, const float *coef_b, int pool_K, const float *Yprev,
                                       long long ldy, const float *scale, const float *shift, const float *mean,
-                                      const float *invstd, float *red_slab, const prifit_bn_bwd *bn, void *stream);
+                                      const float *invstd, float *red_slab, void *stream);
 int prifit_gemm_stream_tn_pool_f32(int Mo, int No, long long P, const float *Y, long long ldy, const float *A,
                                    long long lda, float *out, long long ldo, const float *b_scale,
                                    const float *b_shift, const int32_t *pool_arg, const float *pool_T,
@@ -348,7 +317,7 @@ int prifit_gemm_stream_dgrad_bn_f32(int M, int N, int K, const float *Gin, const
                                     long long ldb, float *G, long long ldc, const float *scale_l, const float *shift_l,
                                     const float *coef_a, const float *coef_b, const float *coef_d, const float *Yprev,
                                     long long ldy, const float *scale, const float *shift, const float *mean,
-                                    const float *invstd, float *red_slab, const prifit_bn_bwd *bn, void *stream);
+                                    const float *invstd, float *red_slab, void *stream);
 int prifit_gemm_stream_tn_f32(int Mo, int No, long long P, const float *G, long long ldg, const float *A,
                               long long lda, float *out, long long ldo, const float *b_scale,
                               const float *b_shift, float *workspace, void *stream);
@@ -547,7 +516,7 @@ int prifit_sa_group_linear_fwd(const float *xyz, const float *new_xyz, int B, in
                                const float *radius2, const int *nsample, const int *width, int mode,
                                const float *feat, int D, int feat_first, int feat_xyz, const float *const *W,
                                const float *const *U, const float *const *Vc, const float *const *bias,
-                               float *const *Y, float *const *slab, int32_t *const *idx, const prifit_bn_fwd *const *bn, void *stream);
+                               float *const *Y, float *const *slab, int32_t *const *idx, void *stream);
 /* Queries per statistics slab of the call above (the workgroup size it will pick for B shapes x S centres). */
 int prifit_sa_group_queries_per_slab(int B, int S);
 /* autograd of mode 0 w.r.t. the weight: partial [nblocks][C][D+3] (upstream column order) with
@@ -585,13 +554,13 @@ int prifit_sa_first_layer_dw_bn_gather(const float *G, const float *U, const flo
 int prifit_bn_relu_bwd_reduce(const float *G, long long ldg, const float *Y, long long ldy,
                               const float *scale, const float *shift, const float *mean,
                               const float *invstd, int P, int C, int rows_per_sample, float slope,
-                              float *slab, const prifit_bn_bwd *bn, void *stream);
+                              float *slab, void *stream);
 
 /* The same partials when the gradient gp [G, ldgp] arrives through the group max-pool. */
 int prifit_pool_bwd_reduce(const float *gp, long long ldgp, const float *Y, long long ldy,
                            const int32_t *arg, const float *scale, const float *shift,
                            const float *mean, const float *invstd, int G, int K, int C,
-                           int rows_per_sample, float slope, float *slab, const prifit_bn_bwd *bn, void *stream);
+                           int rows_per_sample, float slope, float *slab, void *stream);
 
 /* m1, m2 -> dgamma, dbeta and the per-channel coefficients of dY = a*(G*mask) + b*Y + d
  * (training != 0: batch-stat BatchNorm backward; training == 0: running-stat affine). */
@@ -693,7 +662,7 @@ int prifit_gemm_stream_bwd_f32(long long P, int Cout, int Cin, const float *G, c
                                const int32_t *pool_arg, const float *pool_T, int pool_K, const float *W, long long ldw,
                                const float *Yp, long long ldyp, const float *p_scale, const float *p_shift,
                                const float *p_mean, const float *p_invstd, float *Gp, long long ldgp, float *red_slab,
-                               float *dW, long long lddw, float *workspace, const prifit_bn_bwd *bn, void *stream);
+                               float *dW, long long lddw, float *workspace, void *stream);
 
 /* Row-sparse backward of `iterations` mean-shift updates, for a loss that reads the shifted points through
  * `center = new_X[indices]` only (src/mean_shift.py:44-46; autograd of :61-82).  Row i of an iterate depends on row i of

@@ -68,6 +68,12 @@ def _signatures(header_path=HEADER_PATH):
     return sigs
 
 
+def abi_version(header_path=HEADER_PATH):
+    """PRIFIT_ABI_VERSION of the public header."""
+    with open(header_path) as f:
+        return int(re.search(r"^#define\s+PRIFIT_ABI_VERSION\s+(\d+)", f.read(), flags=re.M).group(1))
+
+
 def dll():
     global _dll
     if _dll is None:
@@ -75,14 +81,23 @@ def dll():
             raise RuntimeError(
                 "libprifit_hip.so is not built (%s). Run `python -m prifit_amd.build` "
                 "(needs hipcc); there is no CPU fallback." % LIB_PATH)
-        _dll = ctypes.CDLL(LIB_PATH)
+        lib = ctypes.CDLL(LIB_PATH)
+        # the argtypes below come from the header: a library built from another revision of it would be called with its
+        # arguments in the wrong slots, silently
+        lib.prifit_version.restype = ctypes.c_int
+        lib.prifit_version.argtypes = [ctypes.c_void_p]
+        have, want = lib.prifit_version(None), abi_version()
+        if have != want:
+            raise RuntimeError("%s has ABI version %d, include/prifit_hip.h declares %d: rebuild it "
+                               "(python -m prifit_amd.build)" % (LIB_PATH, have, want))
         sigs = _signatures()
         for name, ret in _declared().items():
-            fn = getattr(_dll, name)  # AttributeError if the library lacks a declared symbol
+            fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = ctypes.c_int if ret == "int" else ctypes.c_longlong
             if name not in sigs:
                 raise RuntimeError("prifit_hip.h: no parameter list parsed for %s" % name)
             fn.argtypes = sigs[name]
+        _dll = lib
     return _dll
 
 

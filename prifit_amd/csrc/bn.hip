@@ -5,6 +5,63 @@
 // per-block partial slabs [nblk][2][C] finalised in double precision (deterministic, no atomics).
 #include "common.h"
 
+// The coefficient arithmetic of a BatchNorm layer from its column sums, shared by the finalize kernels below.  Contraction is
+// switched OFF inside these two functions (`#pragma clang fp contract(off)`; HIP's `__dmul_rn` & co. are plain operators that the
+// compiler may still fuse): device code is built with -ffp-contract=fast except the index-critical translation units, and
+// whether `q / n - mean * mean` became a fused multiply-add depended on the surrounding kernel -- which showed as one-ulp
+// differences in the running variance between two arms of the same layer.
+// out: [4][C] at stride C = scale, shift, mean, invstd (forward) / [5][C] = dgamma, dbeta, a, b, d (backward).
+__device__ __forceinline__ void bn_fwd_coefs(double s, double q, double count, float gamma, float beta, float eps, float momentum,
+                                             float *rmean, float *rvar, float *out, int C)
+{
+#pragma clang fp contract(off)
+    const double mean = s / count;
+    const double msq = mean * mean;
+    double var = q / count - msq;
+    var = var > 0.0 ? var : 0.0;
+    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+    const float sc = gamma * invstd;
+    const float msc = (float)mean * sc;
+    out[0] = sc;
+    out[C] = beta - msc;
+    out[2 * C] = (float)mean;
+    out[3 * C] = invstd;
+    if (rmean) {
+        const double vc = var * count;
+        const double unbiased = count > 1.0 ? vc / (count - 1.0) : var;
+        const float keep = 1.f - momentum;
+        const float km = keep * *rmean, mm = momentum * (float)mean;
+        const float kv = keep * *rvar, mv = momentum * (float)unbiased;
+        *rmean = km + mm;
+        *rvar = kv + mv;
+    }
+}
+
+//   train: dY = gamma*invstd * (Gm - m1/n - yhat * m2/n)        eval: dY = gamma*invstd_running * Gm  (b = d = 0)
+__device__ __forceinline__ void bn_bwd_coefs(double m1, double m2, double count, int training, float scale, float mean, float invstd,
+                                             float *out, int C)
+{
+#pragma clang fp contract(off)
+    out[0] = (float)m2;           // dgamma
+    out[C] = (float)m1;           // dbeta
+    const double a = (double)scale;  // gamma * invstd
+    out[2 * C] = (float)a;
+    if (training) {
+        const double is = (double)invstd, mu = (double)mean;
+        const double m2n = m2 / count, m1n = m1 / count;
+        const double ais = a * is;
+        const double b = ais * m2n;
+        const double muis = mu * is;
+        const double t = muis * m2n;
+        const double d = a * (t - m1n);
+        out[3 * C] = (float)(-b);
+        out[4 * C] = (float)d;
+    } else {
+        out[3 * C] = 0.f;
+        out[4 * C] = 0.f;
+    }
+}
+
 constexpr int RED_ROWS = 128;  // rows of the matrix reduced by one workgroup
 
 __device__ __forceinline__ float4 ld4g(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -15,10 +72,9 @@ __device__ __forceinline__ void st4g(float *p, float4 v) { *reinterpret_cast<flo
 constexpr int POOL_RED_ROWS = 16;  // groups per workgroup in the pooled-layer reduction (only G = P/K rows: keep the grid wide)
 
 template <int ROWS = RED_ROWS, typename F>
-__device__ __forceinline__ void column_reduce(int P, int C, float *__restrict__ slab, F f, const BnTail &tail = BnTail{})
+__device__ __forceinline__ void column_reduce(int P, int C, float *__restrict__ slab, F f)
 {
     __shared__ float4 s_red[2][256];
-    __shared__ int s_tail;
     const int C4 = C >> 2;
     const int r_begin = blockIdx.x * ROWS, r_end = min(P, r_begin + ROWS);
     for (int cbase = 0; cbase < C4; cbase += 256) {
@@ -38,19 +94,11 @@ __device__ __forceinline__ void column_reduce(int P, int C, float *__restrict__ 
                 t0.x += u0.x; t0.y += u0.y; t0.z += u0.z; t0.w += u0.w;
                 t1.x += u1.x; t1.y += u1.y; t1.z += u1.z; t1.w += u1.w;
             }
-            if (tail.acc) {   // the sums finalized by this launch (common.h) instead of one slab per workgroup
-                bn_tail_add(tail, 0, 4 * c4, t0.x); bn_tail_add(tail, 0, 4 * c4 + 1, t0.y);
-                bn_tail_add(tail, 0, 4 * c4 + 2, t0.z); bn_tail_add(tail, 0, 4 * c4 + 3, t0.w);
-                bn_tail_add(tail, 1, 4 * c4, t1.x); bn_tail_add(tail, 1, 4 * c4 + 1, t1.y);
-                bn_tail_add(tail, 1, 4 * c4 + 2, t1.z); bn_tail_add(tail, 1, 4 * c4 + 3, t1.w);
-            } else {
-                st4g(slab + ((size_t)blockIdx.x * 2 + 0) * C + 4 * c4, t0);
-                st4g(slab + ((size_t)blockIdx.x * 2 + 1) * C + 4 * c4, t1);
-            }
+            st4g(slab + ((size_t)blockIdx.x * 2 + 0) * C + 4 * c4, t0);
+            st4g(slab + ((size_t)blockIdx.x * 2 + 1) * C + 4 * c4, t1);
         }
         __syncthreads();
     }
-    if (tail.acc) bn_tail_finish(tail, &s_tail);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -625,7 +673,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float *__
                                                                  const float *__restrict__ shift,
                                                                  const float *__restrict__ mean,
                                                                  const float *__restrict__ invstd, int P, int C,
-                                                                 int rps, float slope, float *__restrict__ slab, const BnTail tail)
+                                                                 int rps, float slope, float *__restrict__ slab)
 {
     column_reduce(P, C, slab, [&](int r, int c4, float4 &a0, float4 &a1) {
         const int c = 4 * c4;
@@ -637,7 +685,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float *__
         a0.x += gx; a0.y += gy; a0.z += gz; a0.w += gw;
         a1.x += gx * ((y.x - mu.x) * is.x); a1.y += gy * ((y.y - mu.y) * is.y);
         a1.z += gz * ((y.z - mu.z) * is.z); a1.w += gw * ((y.w - mu.w) * is.w);
-    }, tail);
+    });
 }
 
 // Same partials when the gradient arrives through the group max-pool: only the winning sample of
@@ -650,7 +698,7 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float *__res
                                                               const float *__restrict__ mean,
                                                               const float *__restrict__ invstd, int G, int K,
                                                               int C, int rps, float slope,
-                                                              float *__restrict__ slab, const BnTail tail)
+                                                              float *__restrict__ slab)
 {
     column_reduce<POOL_RED_ROWS>(G, C, slab, [&](int gi, int c4, float4 &a0, float4 &a1) {
         const int c = 4 * c4;
@@ -666,7 +714,7 @@ __global__ __launch_bounds__(256) void pool_bwd_reduce_kernel(const float *__res
         a0.x += gx; a0.y += gy; a0.z += gz; a0.w += gw;
         a1.x += gx * ((yx - mu.x) * is.x); a1.y += gy * ((yy - mu.y) * is.y);
         a1.z += gz * ((yz - mu.z) * is.z); a1.w += gw * ((yw - mu.w) * is.w);
-    }, tail);
+    });
 }
 
 // m1, m2 -> dgamma = m2, dbeta = m1 and the coefficients of dY = a * Gmasked + b * Y + d:
@@ -1094,34 +1142,29 @@ int prifit_gather_linear_bwd_bn(const float *G, const float *Y, const float *sca
     return prifit_check_launch();
 }
 
-int prifit_bn_tail_replicas(void) { return BN_TAIL_REPLICAS; }
-
 int prifit_bn_relu_bwd_reduce(const float *G, long long ldg, const float *Y, long long ldy, const float *scale,
                               const float *shift, const float *mean, const float *invstd, int P, int C,
-                              int rows_per_sample, float slope, float *slab, const prifit_bn_bwd *bn, void *stream)
+                              int rows_per_sample, float slope, float *slab, void *stream)
 {
-    const bool tail = bn && bn->acc;
-    if (bad_mat(G, ldg, C) || bad_mat(Y, ldy, C) || !scale || !shift || !mean || !invstd || (!slab && !tail) || P <= 0 ||
-        rows_per_sample < 0 || (rows_per_sample % RED_ROWS) != 0 || bn_bwd_bad(bn) || (tail && rows_per_sample != 0))
+    if (bad_mat(G, ldg, C) || bad_mat(Y, ldy, C) || !scale || !shift || !mean || !invstd || !slab || P <= 0 ||
+        rows_per_sample < 0 || (rows_per_sample % RED_ROWS) != 0)
         return PRIFIT_EINVAL;
     hipLaunchKernelGGL(bn_relu_bwd_reduce_kernel, dim3((P + RED_ROWS - 1) / RED_ROWS), dim3(256), 0,
                        as_stream(stream), G, ldg, Y, ldy, scale, shift, mean, invstd, P, C, rows_per_sample, slope,
-                       slab, bn_tail_bwd(bn, C));
+                       slab);
     return prifit_check_launch();
 }
 
 int prifit_pool_bwd_reduce(const float *gp, long long ldgp, const float *Y, long long ldy, const int32_t *arg,
                            const float *scale, const float *shift, const float *mean, const float *invstd, int G,
-                           int K, int C, int rows_per_sample, float slope, float *slab, const prifit_bn_bwd *bn, void *stream)
+                           int K, int C, int rows_per_sample, float slope, float *slab, void *stream)
 {
-    const bool tail = bn && bn->acc;
-    if (bad_mat(gp, ldgp, C) || bad_mat(Y, ldy, C) || !arg || !scale || !shift || !mean || !invstd || (!slab && !tail) ||
-        G <= 0 || K <= 0 || rows_per_sample < 0 || (rows_per_sample % (K * POOL_RED_ROWS)) != 0 || bn_bwd_bad(bn) ||
-        (tail && rows_per_sample != 0))
+    if (bad_mat(gp, ldgp, C) || bad_mat(Y, ldy, C) || !arg || !scale || !shift || !mean || !invstd || !slab ||
+        G <= 0 || K <= 0 || rows_per_sample < 0 || (rows_per_sample % (K * POOL_RED_ROWS)) != 0)
         return PRIFIT_EINVAL;
     hipLaunchKernelGGL(pool_bwd_reduce_kernel, dim3((G + POOL_RED_ROWS - 1) / POOL_RED_ROWS), dim3(256), 0,
                        as_stream(stream), gp, ldgp, Y, ldy, arg, scale, shift, mean, invstd, G, K, C, rows_per_sample,
-                       slope, slab, bn_tail_bwd(bn, C));
+                       slope, slab);
     return prifit_check_launch();
 }
 

@@ -55,7 +55,6 @@ struct GemmArgs {
     int vecA, vecB;                  // 16-byte loads legal for the operand
     int ntiles;                      // gemm_pers_kernel: output tiles, walked with a grid stride
     float *cand;                     // gemm_pers_kernel<.., PMAX>: [M / 32][4][N] pool candidates
-    BnTail tail;                     // the column sums `stats` would receive, finalized by this launch instead (common.h)
 };
 
 #ifndef GEMM_W8
@@ -657,8 +656,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, ((BM / WM) * (BN / WN) 
             }
         }
     }
-    const bool tail = g.tail.acc != nullptr;
-    if (g.stats || tail) {
+    if (g.stats) {
         __syncthreads();  // LDS tiles are dead: reuse as [WAVES_M][2][BN]
         float *red = lds;
 #pragma unroll
@@ -676,12 +674,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, ((BM / WM) * (BN / WN) 
             float s = 0.f;
 #pragma unroll
             for (int w = 0; w < BM / WM; ++w) s += red[(w * 2 + which) * BN + c];
-            if (n0 + c < g.N) {
-                if (tail) bn_tail_add(g.tail, which, n0 + c, s);
-                else g.stats[((long long)tile_m * 2 + which) * g.N + n0 + c] = s;
-            }
+            if (n0 + c < g.N) g.stats[((long long)tile_m * 2 + which) * g.N + n0 + c] = s;
         }
-        if (tail) bn_tail_finish(g.tail, reinterpret_cast<int *>(lds));   // (its first barrier: `red` is read; lds[0] becomes the flag)
     }
 }
 
@@ -832,7 +826,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                                  : __builtin_amdgcn_raw_buffer_load_b32(yrs, cok ? y_voff + ro : y_voff, 0, 0));
                 }
             }
-            float vmax = -INFINITY, vmin = INFINITY;
+            float vmax = -INFINITY, vmin = INFINITY, v0 = 0.f;
             int imax = 0, imin = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -851,7 +845,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                     csq[b] += gm * ((kf[r] - rmu) * ris);
                 } else {
                     csum[b] += vs;
-                    csq[b] += vs * vs;
+                    // sum of squares in a fixed rounding order, fma(v0, v0, v1 * v1) and then one fma per row: written out,
+                    // because -ffp-contract=fast leaves the pairing of the first two squares to the compiler, and its choice
+                    // moved with unrelated code of this kernel
+                    if (r == 0) v0 = vs;
+                    else if (r == 1) csq[b] = fmaf(v0, v0, vs * vs);
+                    else csq[b] = fmaf(vs, vs, csq[b]);
                 }
                 {
                     const int ro = ((r & 3) + 8 * (r >> 2)) * ldc4;
@@ -873,7 +872,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
         }
         PERS_STAMP(3);
-        if (g.stats || g.tail.acc) {
+        if (g.stats) {
             float *red = lds;   // both stages are dead: everybody passed the barrier that ended the k-loop
 #pragma unroll
             for (int b = 0; b < TN; ++b) {
@@ -890,12 +889,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 float s = 0.f;
 #pragma unroll
                 for (int w = 0; w < BM / WM; ++w) s += red[(w * 2 + which) * BN + c];
-                if (n0 + c < g.N) {
-                    if (g.tail.acc) bn_tail_add(g.tail, which, n0 + c, s);
-                    else g.stats[((long long)tile_m * 2 + which) * g.N + n0 + c] = s;
-                }
+                if (n0 + c < g.N) g.stats[((long long)tile_m * 2 + which) * g.N + n0 + c] = s;
             }
-            if (has_next || g.tail.acc) __syncthreads();   // `red` is read before the next tile is staged over it
+            if (has_next) __syncthreads();   // `red` is read before the next tile is staged over it
         }
         PERS_STAMP(4);
         if (!has_next) break;
@@ -908,7 +904,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         ++st_tile;
 #endif
     }
-    if (g.tail.acc) bn_tail_finish(g.tail, reinterpret_cast<int *>(lds));   // (after the last tile's barrier: lds is free)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1148,7 +1143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // the split-K kernel's cases: TN, one batch item, no epilogue / statistics / bias / A prologue, 16-byte rows, spans < 2 GiB
 static bool launch_tnsk(const GemmArgs &g, hipStream_t st)
 {
-    if (g.batch != 1 || g.a_scale || g.bias || g.stats || g.tail.acc || g.epi != EPI_NONE || g.a_rowsum || g.kswitch ||
+    if (g.batch != 1 || g.a_scale || g.bias || g.stats || g.epi != EPI_NONE || g.a_rowsum || g.kswitch ||
         !(g.vecA && g.vecB) || (g.M & 3) || (g.N & 3) || (g.splitk > 1 && !g.accumulate) || g.splitk > 65535)
         return false;
     const long long lim = 0x7ff00000LL;
@@ -1374,11 +1369,8 @@ int prifit_gemm_f32(int layout, int M, int N, int K, const float *A, long long l
                     long long strideC, int batch, int splitk, const float *a_scale, const float *a_shift,
                     const float *b_scale, const float *b_shift, const float *bias, long long bias_batch_stride,
                     float *col_stats, int epilogue, const float *epi_batch_scalar, const float *epi_aux, long long ld_aux,
-                    long long stride_aux, const float *epi_row_add, float *a_rowsum, int accumulate,
-                    const prifit_bn_fwd *bn, void *stream)
+                    long long stride_aux, const float *epi_row_add, float *a_rowsum, int accumulate, void *stream)
 {
-    const bool has_tail = bn && bn->acc;
-    if (bn_fwd_bad(bn) || (has_tail && (batch != 1 || splitk != 1 || epilogue != EPI_NONE))) return PRIFIT_EINVAL;
     if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || splitk <= 0 || layout < 0 || layout > 2 ||
         (epilogue != 100 && (epilogue < 0 || epilogue > 3)) || (epilogue >= EPI_MSKERNEL && !epi_batch_scalar) ||
         (epilogue == EPI_MSBWD && !epi_aux) || (splitk > 1 && !accumulate) ||
@@ -1386,7 +1378,6 @@ int prifit_gemm_f32(int layout, int M, int N, int K, const float *A, long long l
         (col_stats && (batch != 1 || splitk != 1)) || (epilogue != EPI_NONE && epilogue != 100 && splitk != 1) || (long long)batch * splitk > 65535)
         return PRIFIT_EINVAL;
     GemmArgs g;
-    g.tail = BnTail{};
     g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = strideA; g.sB = strideB; g.sC = strideC;
     g.batch = batch; g.splitk = splitk;
@@ -1396,7 +1387,6 @@ int prifit_gemm_f32(int layout, int M, int N, int K, const float *A, long long l
     g.row_add = epi_row_add; g.a_rowsum = a_rowsum;
     g.red_scale = g.red_shift = g.red_mean = g.red_invstd = nullptr;
     g.dA2 = g.dB2 = 0; g.kswitch = 0;
-    g.tail = bn_tail_fwd(bn, N);
     if (a_rowsum && (layout == LAY_TN || splitk != 1)) return PRIFIT_EINVAL;
     return dispatch(g, layout, stream);
 }
@@ -1413,7 +1403,6 @@ int prifit_gemm_dual_nn_f32(int M, int N, int K1, int K2, const float *A1, const
     // the vector path needs both sources equally aligned
     if ((((uintptr_t)A1 ^ (uintptr_t)A2) | ((uintptr_t)B1 ^ (uintptr_t)B2)) & 15) return PRIFIT_EINVAL;
     GemmArgs g;
-    g.tail = BnTail{};
     g.A = A1; g.B = B1; g.C = C; g.M = M; g.N = N; g.K = K1 + K2;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = strideA; g.sB = strideB; g.sC = strideC;
     g.batch = batch; g.splitk = splitk;
@@ -1446,14 +1435,12 @@ int prifit_gemm_dual_nn_f32(int M, int N, int K1, int K2, const float *A1, const
 
 int prifit_gemm_dgrad_bnred_f32(int M, int N, int K, const float *dY, long long lda, const float *W, long long ldb,
                                 float *G, long long ldc, const float *Yprev, long long ldy, const float *scale,
-                                const float *shift, const float *mean, const float *invstd, float *red_slab,
-                                const prifit_bn_bwd *bn, void *stream)
+                                const float *shift, const float *mean, const float *invstd, float *red_slab, void *stream)
 {
-    if (!dY || !W || !G || !Yprev || !scale || !shift || !mean || !invstd || (!red_slab && !(bn && bn->acc)) || bn_bwd_bad(bn) || M <= 0 || N <= 0 || K <= 0 ||
+    if (!dY || !W || !G || !Yprev || !scale || !shift || !mean || !invstd || !red_slab || M <= 0 || N <= 0 || K <= 0 ||
         lda < K || ldb < N || ldc < N || ldy < N)
         return PRIFIT_EINVAL;
     GemmArgs g;
-    g.tail = BnTail{};
     g.A = dY; g.B = W; g.C = G; g.M = M; g.N = N; g.K = K;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = g.sB = g.sC = 0;
     g.batch = 1; g.splitk = 1;
@@ -1462,7 +1449,6 @@ int prifit_gemm_dgrad_bnred_f32(int M, int N, int K, const float *dY, long long 
     g.accumulate = 0; g.aux = Yprev; g.ldaux = ldy; g.sAux = 0; g.row_add = nullptr; g.a_rowsum = nullptr;
     g.red_scale = scale; g.red_shift = shift; g.red_mean = mean; g.red_invstd = invstd;
     g.dA2 = g.dB2 = 0; g.kswitch = 0;
-    g.tail = bn_tail_bwd(bn, N);
     return dispatch(g, LAY_NN, stream);
 }
 
@@ -1523,7 +1509,6 @@ int prifit_gemm_pool_supported(int M, int N, int K)
 {
     if (M <= 0 || N <= 96 || K <= 0 || (M & 31)) return 0;
     GemmArgs g;
-    g.tail = BnTail{};
     static float dummy[4] __attribute__((aligned(16)));
     pool_gemm_args(g, M, N, K, dummy, K, dummy, K, dummy, N, dummy, dummy, nullptr, nullptr);
     return launch_persistent(g, LAY_NT, nullptr, nullptr, true) ? 1 : 0;
@@ -1531,16 +1516,13 @@ int prifit_gemm_pool_supported(int M, int N, int K)
 
 int prifit_gemm_pool_f32(int M, int N, int K, const float *A, long long lda, const float *W, long long ldb, float *Y,
                          long long ldc, const float *a_scale, const float *a_shift, const float *bias, float *col_stats,
-                         float *cand, const prifit_bn_fwd *bn, void *stream)
+                         float *cand, void *stream)
 {
-    if (bn_fwd_bad(bn)) return PRIFIT_EINVAL;
     if (!A || !W || ((a_scale == nullptr) != (a_shift == nullptr)) || !cand || !prifit_gemm_pool_supported(M, N, K) ||
         lda < K || ldb < K || ldc < N)
         return PRIFIT_EINVAL;
     GemmArgs g;
-    g.tail = BnTail{};
     pool_gemm_args(g, M, N, K, A, lda, W, ldb, Y, ldc, a_scale, a_shift, bias, col_stats);
-    g.tail = bn_tail_fwd(bn, N);
     if (!launch_persistent(g, LAY_NT, as_stream(stream), cand)) return PRIFIT_EINVAL;
     return prifit_check_launch();
 }

@@ -43,7 +43,6 @@ struct BwdArgs {
     float *red_slab;                          // [grid][2][Cin]
     float *dw_part;                           // [grid][Cout][Cin]
     GatherSrc gs;                             // GATH: Yp is not stored, its rows are re-formed from (idx, U, Vc) -- common.h
-    BnTail tail;                              // the (m1, m2) sums finalized by this launch instead of written to red_slab (common.h)
 };
 
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
@@ -77,7 +76,6 @@ __global__ __launch_bounds__((64 * Roles<COUT, CIN>::NW), 1) void gemm_stream_bw
     __shared__ __attribute__((aligned(16))) float s_dy[2][SBM * LDY];
     __shared__ __attribute__((aligned(16))) float s_p[2][SBM * LDP];
     __shared__ __attribute__((aligned(16))) float s_co[5][COUT];   // s, t, a, b, d
-    __shared__ int s_tail;
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int li = lane & 31, lh = lane >> 5;
@@ -307,13 +305,8 @@ __global__ __launch_bounds__((64 * Roles<COUT, CIN>::NW), 1) void gemm_stream_bw
         m1 += __shfl_xor(m1, 32, 64);
         m2 += __shfl_xor(m2, 32, 64);
         if (lh == 0) {
-            if (g.tail.acc) {
-                bn_tail_add(g.tail, 0, col, m1);
-                bn_tail_add(g.tail, 1, col, m2);
-            } else {
-                g.red_slab[((long long)blockIdx.x * 2 + 0) * CIN + col] = m1;
-                g.red_slab[((long long)blockIdx.x * 2 + 1) * CIN + col] = m2;
-            }
+            g.red_slab[((long long)blockIdx.x * 2 + 0) * CIN + col] = m1;
+            g.red_slab[((long long)blockIdx.x * 2 + 1) * CIN + col] = m2;
         }
     } else {
         // dW accumulators of this wave's blocks for the life of the workgroup; block id = (cout block) * NA + (cin block)
@@ -390,7 +383,6 @@ __global__ __launch_bounds__((64 * Roles<COUT, CIN>::NW), 1) void gemm_stream_bw
         if constexpr (R::NW > NA + 2) { if (wave == NA + 2) w_role(IC<R::wb0[NA + 2]>{}, IC<R::wcnt[NA + 2]>{}); }
         if constexpr (R::NW > NA + 3) { if (wave == NA + 3) w_role(IC<R::wb0[NA + 3]>{}, IC<R::wcnt[NA + 3]>{}); }
     }
-    if (g.tail.acc) bn_tail_finish(g.tail, &s_tail);      // every wave of both roles arrives here
 }
 
 // dW[c] = sum over workgroups of their partial slabs, in a fixed order: 64 outputs per workgroup, four threads per output
@@ -471,10 +463,9 @@ static int stream_bwd_impl(long long P, int Cout, int Cin, const float *G, const
                            const int32_t *pool_arg, const float *pool_T, int pool_K, const float *W, long long ldw,
                            const float *Yp, long long ldyp, const float *p_scale, const float *p_shift,
                            const float *p_mean, const float *p_invstd, float *Gp, long long ldgp, float *red_slab,
-                           float *dW, long long lddw, float *workspace, const GatherSrc *gs, const prifit_bn_bwd *bn, void *stream)
+                           float *dW, long long lddw, float *workspace, const GatherSrc *gs, void *stream)
 {
     const bool pool = pool_arg != nullptr;
-    if (bn_bwd_bad(bn)) return PRIFIT_EINVAL;
     if (gs) {   // Yp re-formed from (idx, U, Vc): middle layers on a 64-wide first layer only
         if (pool || Cin != 64 || !gs->idx || !gs->U || !gs->Vc || gs->N <= 0 || gs->S <= 0 || gs->Kg <= 0 || (gs->Kg % SBM) ||
             gs->C != Cin || P % ((long long)gs->S * gs->Kg) != 0 || (((uintptr_t)gs->U | (uintptr_t)gs->Vc) & 15) ||
@@ -483,7 +474,7 @@ static int stream_bwd_impl(long long P, int Cout, int Cin, const float *G, const
         Yp = gs->U;   // (only checked for presence and alignment below)
         ldyp = Cin;
     }
-    if (!Y || !coef_b || !coef_d || !W || !Yp || !p_scale || !p_shift || !p_mean || !p_invstd || !Gp || (!red_slab && !(bn && bn->acc)) || !dW ||
+    if (!Y || !coef_b || !coef_d || !W || !Yp || !p_scale || !p_shift || !p_mean || !p_invstd || !Gp || !red_slab || !dW ||
         !workspace || !prifit_gemm_stream_bwd_supported(P, Cout, Cin, pool ? pool_K : 0) || ldw < Cin || ldyp < Cin || ldgp < Cin ||
         lddw < Cin || (ldyp & 3) || (pool ? (!pool_T) : (!G || !scale || !shift || !coef_a)) ||
         (((uintptr_t)Y | (uintptr_t)G | (uintptr_t)Yp | (uintptr_t)pool_arg | (uintptr_t)pool_T) & 15) ||
@@ -494,7 +485,6 @@ static int stream_bwd_impl(long long P, int Cout, int Cin, const float *G, const
     g.pool_arg = pool_arg; g.pool_T = pool_T; g.pool_K = pool ? pool_K : 1;
     g.W = W; g.ldw = ldw; g.Yp = Yp; g.ldyp = ldyp; g.ps = p_scale; g.pt = p_shift; g.pmu = p_mean; g.pis = p_invstd;
     g.Gp = Gp; g.ldgp = ldgp; g.red_slab = red_slab; g.dw_part = workspace;
-    g.tail = bn_tail_bwd(bn, Cin);
     g.gs.idx = nullptr;
     if (gs) {
         g.gs = *gs;
@@ -517,10 +507,10 @@ int prifit_gemm_stream_bwd_f32(long long P, int Cout, int Cin, const float *G, c
                                const int32_t *pool_arg, const float *pool_T, int pool_K, const float *W, long long ldw,
                                const float *Yp, long long ldyp, const float *p_scale, const float *p_shift,
                                const float *p_mean, const float *p_invstd, float *Gp, long long ldgp, float *red_slab,
-                               float *dW, long long lddw, float *workspace, const prifit_bn_bwd *bn, void *stream)
+                               float *dW, long long lddw, float *workspace, void *stream)
 {
     return stream_bwd_impl(P, Cout, Cin, G, Y, scale, shift, coef_a, coef_b, coef_d, pool_arg, pool_T, pool_K, W, ldw, Yp, ldyp,
-                           p_scale, p_shift, p_mean, p_invstd, Gp, ldgp, red_slab, dW, lddw, workspace, nullptr, bn, stream);
+                           p_scale, p_shift, p_mean, p_invstd, Gp, ldgp, red_slab, dW, lddw, workspace, nullptr, stream);
 }
 
 int prifit_gemm_stream_bwd_gather_f32(long long P, int Cout, const float *G, const float *Y, const float *scale,
@@ -528,12 +518,11 @@ int prifit_gemm_stream_bwd_gather_f32(long long P, int Cout, const float *G, con
                                       const float *W, long long ldw, const int32_t *idx, const float *U, const float *Vc,
                                       int n_points, int n_centres, int rows_per_centre, const float *p_scale,
                                       const float *p_shift, const float *p_mean, const float *p_invstd, float *Gp, long long ldgp,
-                                      float *red_slab, float *dW, long long lddw, float *workspace, const prifit_bn_bwd *bn,
-                                      void *stream)
+                                      float *red_slab, float *dW, long long lddw, float *workspace, void *stream)
 {
     const GatherSrc gs = {idx, U, Vc, n_points, n_centres, rows_per_centre, 64, 0u};
     return stream_bwd_impl(P, Cout, 64, G, Y, scale, shift, coef_a, coef_b, coef_d, nullptr, nullptr, 0, W, ldw, nullptr, 64,
-                           p_scale, p_shift, p_mean, p_invstd, Gp, ldgp, red_slab, dW, lddw, workspace, &gs, bn, stream);
+                           p_scale, p_shift, p_mean, p_invstd, Gp, ldgp, red_slab, dW, lddw, workspace, &gs, stream);
 }
 
 }  // extern "C"

@@ -515,7 +515,7 @@ extern "C" {
 int prifit_version(const char **arch)
 {
     if (arch) *arch = "gfx950";
-    return 100;
+    return PRIFIT_ABI_VERSION;
 }
 
 int prifit_fps(const float *xyz, int B, int N, int npoint, const int64_t *start_idx, int64_t *out_idx,

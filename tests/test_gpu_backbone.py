@@ -273,9 +273,9 @@ def test_bn_apply_on_load_matches_apply_pass(nn_ops, P, Cout, Kin):
     Gp_ref, Gp = torch.empty(P, Kin, device="cuda"), torch.full((P, Kin), float("nan"), device="cuda")
     sl_ref, sl = torch.empty(ns, 2, Kin, device="cuda"), torch.full((ns, 2, Kin), float("nan"), device="cuda")
     call("prifit_gemm_stream_dgrad_f32", P, Kin, Cout, ptr(dY), _LL(Cout), ptr(W), _LL(Kin), ptr(Gp_ref), _LL(Kin), ptr(A), _LL(Kin),
-         ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), None, cur_stream())
+         ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), cur_stream())
     call("prifit_gemm_stream_dgrad_bn_f32", P, Kin, Cout, ptr(G), ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(Gp), _LL(Kin), ptr(s), ptr(t),
-         ptr(ca), ptr(cb), ptr(cd), ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl), None, cur_stream())
+         ptr(ca), ptr(cb), ptr(cd), ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl), cur_stream())
     assert torch.equal(Gp, Gp_ref)
     torch.testing.assert_close(sl.double().sum(0), sl_ref.double().sum(0), rtol=1e-6, atol=1e-3)
 
@@ -306,7 +306,7 @@ def test_fused_da_dw_kernel_matches_separate_streaming_kernels(nn_ops, P, Cout, 
         call("prifit_gemm_stream_tn_pool_f32", Cout, Kin, _LL(P), ptr(Y), _LL(Cout), ptr(A), _LL(Kin), ptr(dW_ref), _LL(Kin), ptr(s1),
              ptr(t1), ptr(arg), ptr(T), ptr(cb), ptr(cd), pool_K, ptr(ws), cur_stream())
         call("prifit_gemm_stream_dgrad_pool_f32", P, Kin, Cout, ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(Gp_ref), _LL(Kin), ptr(bias_dw),
-             ptr(arg), ptr(T), ptr(cb), pool_K, ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), None, cur_stream())
+             ptr(arg), ptr(T), ptr(cb), pool_K, ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), cur_stream())
         G = None
     else:
         G = _rand((P, Cout), 61).cuda()
@@ -314,7 +314,7 @@ def test_fused_da_dw_kernel_matches_separate_streaming_kernels(nn_ops, P, Cout, 
         call("prifit_gemm_stream_tn_bn_f32", Cout, Kin, _LL(P), ptr(G), ptr(Y), _LL(Cout), ptr(A), _LL(Kin), ptr(dW_ref), _LL(Kin), ptr(s1),
              ptr(t1), ptr(s), ptr(t), ptr(ca), ptr(cb), ptr(cd), ptr(ws), cur_stream())
         call("prifit_gemm_stream_dgrad_bn_f32", P, Kin, Cout, ptr(G), ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(Gp_ref), _LL(Kin), ptr(s), ptr(t),
-             ptr(ca), ptr(cb), ptr(cd), ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), None, cur_stream())
+             ptr(ca), ptr(cb), ptr(cd), ptr(A), _LL(Kin), ptr(s1), ptr(t1), ptr(mu1), ptr(is1), ptr(sl_ref), cur_stream())
     ns = dll().prifit_gemm_stream_bwd_slabs(_LL(P), Cout, Kin)
     Gp = torch.full((P, Kin), float("nan"), device="cuda")
     sl = torch.full((ns, 2, Kin), float("nan"), device="cuda")
@@ -322,7 +322,7 @@ def test_fused_da_dw_kernel_matches_separate_streaming_kernels(nn_ops, P, Cout, 
     ws2 = torch.empty(dll().prifit_gemm_stream_bwd_workspace(_LL(P), Cout, Kin), device="cuda")
     call("prifit_gemm_stream_bwd_f32", _LL(P), Cout, Kin, ptr(G), ptr(Y), ptr(None if pool_K else s), ptr(None if pool_K else t),
          ptr(None if pool_K else ca), ptr(cb), ptr(cd), ptr(arg), ptr(T), pool_K, ptr(W), _LL(Kin), ptr(A), _LL(Kin), ptr(s1), ptr(t1),
-         ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(sl), ptr(dW), _LL(Kin), ptr(ws2), None, cur_stream())
+         ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(sl), ptr(dW), _LL(Kin), ptr(ws2), cur_stream())
     assert torch.isfinite(Gp).all() and torch.isfinite(dW).all() and torch.isfinite(sl).all()
     assert (Gp - Gp_ref).abs().max() <= 2e-5 * Gp_ref.abs().max()
     assert (dW - dW_ref).norm() <= 2e-6 * dW_ref.norm()
@@ -344,7 +344,7 @@ def test_pool_candidates_match_pool_fwd(nn_ops, P, K, N, Kin):
     cand = torch.empty(P // 32, 4, N, device="cuda")
     slab = torch.empty(nn_ops.gemm_stats_slabs(P, N, Kin), 2, N, device="cuda")
     call("prifit_gemm_stream_pool_f32", P, N, Kin, ptr(Ad), _LL(Kin), ptr(Wd), _LL(Kin), ptr(Y), _LL(N), ptr(sc.cuda()),
-         ptr(sh.cuda()), ptr(bias.cuda()), ptr(slab), ptr(cand), None, cur_stream())
+         ptr(sh.cuda()), ptr(bias.cuda()), ptr(slab), ptr(cand), cur_stream())
     G = P // K
     s2d, t2d = s2.cuda(), t2.cuda()
     out1, arg1 = torch.empty(G, N, device="cuda"), torch.empty(G, N, dtype=torch.int32, device="cuda")

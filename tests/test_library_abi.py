@@ -16,7 +16,7 @@ def test_header_symbols_exported(hiplib):
 def test_version_and_arch(hiplib):
     arch = ctypes.c_char_p()
     v = hiplib.prifit_version(ctypes.byref(arch))
-    assert v >= 100 and arch.value == b"gfx950"
+    assert v == _lib.abi_version() and v > 100 and arch.value == b"gfx950"
 
 
 def test_code_object_is_gfx950():
@@ -80,3 +80,34 @@ def test_compat_aliases_resolve_to_backend(hiplib):
             if k.split(".")[0] in ("models", "src", "convex_loss"):
                 del sys.modules[k]
         sys.modules.update({k: v for k, v in saved.items() if v is not None})
+
+
+def test_call_sites_match_header():
+    """Every `call("prifit_...", ...)` with a literal name passes as many arguments as the header declares: ctypes accepts
+    surplus arguments without complaint, so a stale call site would shift its arguments silently."""
+    import ast
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sigs = _lib._signatures()
+    sites, bad = 0, []
+    for top in ("prifit_amd", "tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(root, top)):
+            for fn in sorted(f for f in files if f.endswith(".py")):
+                path = os.path.join(dirpath, fn)
+                with open(path) as f:
+                    tree = ast.parse(f.read(), filename=path)
+                for node in ast.walk(tree):
+                    if not (isinstance(node, ast.Call) and node.args and isinstance(node.args[0], ast.Constant) and
+                            isinstance(node.args[0].value, str) and node.args[0].value.startswith("prifit_")):
+                        continue
+                    func = node.func
+                    if (func.id if isinstance(func, ast.Name) else getattr(func, "attr", None)) != "call":
+                        continue
+                    name, nargs = node.args[0].value, len(node.args) - 1
+                    assert not any(isinstance(a, ast.Starred) for a in node.args), "%s:%d" % (path, node.lineno)
+                    sites += 1
+                    if name not in sigs or len(sigs[name]) != nargs:
+                        bad.append("%s:%d %s: %d arguments, header %s" % (os.path.relpath(path, root), node.lineno, name, nargs,
+                                                                         len(sigs[name]) if name in sigs else "-"))
+    assert sites >= 100, sites
+    assert not bad, "\n".join(bad)
