@@ -7,8 +7,10 @@ followed by the max over the K samples of each group (models/pointnet_util.py:19
 layer's BatchNorm+ReLU while loading ("normalise on load") and whose epilogue emits the partial
 sums for its own BatchNorm, so no normalised activation is ever written to HBM.
 """
+import collections
 import ctypes
 import os
+import types
 
 import torch
 
@@ -37,9 +39,6 @@ _FUSE_POOL = os.environ.get("PRIFIT_FUSE_POOL_BWD", "1") != "0"  # 0: pool_bwd_a
 # where it measured faster -- the unpooled middle layers (_FUSE_BWD_AUTO below; round 3 had only the 96 -> 64 one);
 # "1": every supported shape (slower on the others: the kernel's dW role is latency-bound); "0": never.
 _FUSE_BWD = os.environ.get("PRIFIT_FUSE_DA_DW", "auto")
-# (round 5 carried an opt-in algebraic form of the max-pooled set-abstraction layers' backward here, PRIFIT_POOL_ALG: parity-green,
-# its dense pass 30-55 % faster than the dA / dW pair, slower on the step because of the winners' index work; removed in round 6,
-# the measurements are in DESIGN.md Appendix A.  The layer pooled over the WHOLE cloud keeps that form: src/dgcnn.py.)
 
 # (round 4, tools/fam_table.py on one box: one-pass kernel against the separate dA + dW pair)
 #   [1.57 M x 96 x 64] 546 / 712 us, [786 K x 64 x 64] 171 / 282, [197 K x 128 x 128] 152 / 176, [49 K x 128 x 128] 54 / 72;
@@ -50,7 +49,12 @@ _FUSE_BWD_AUTO = {(96, 64), (64, 64), (128, 128)}
 def _fuse_bwd_on(Cout, Kin, pooled):
     if _FUSE_BWD == "auto":
         return (Cout, Kin) in _FUSE_BWD_AUTO and not pooled
-    return _FUSE_BWD not in ("0", "", False)
+    return _FUSE_BWD not in ("0", "")
+
+
+def _bn_tile(N):
+    """Column tile of the tiled kernel's instantiation for N output columns (the span names carry it)."""
+    return 32 if N <= 32 else (64 if N <= 64 else (96 if N <= 96 else 128))
 
 
 def _stream_ok(layout, M, N, K, batch=1, splitk=1, epi=EPI_NONE, b_affine=None, a_rowsum=None, accumulate=False,
@@ -94,8 +98,8 @@ def gemm(layout, M, N, K, A, lda, B, ldb, C, ldc, batch=1, sA=0, sB=0, sC=0, spl
                  cur_stream())
         return
     # span name = the kernel instantiation (layout, BN tile) so that it lines up with rocprofv3's per-kernel rows
-    with profiler.span(profiler.tag("gemm_%s_bn%d" % (("nt", "nn", "tn")[layout], 32 if N <= 32 else (64 if N <= 64 else (96 if N <= 96 else 128))),
-                                    M, N, K, batch, splitk), 2.0 * M * N * K * batch):
+    with profiler.span(profiler.tag("gemm_%s_bn%d" % (("nt", "nn", "tn")[layout], _bn_tile(N)), M, N, K, batch, splitk),
+                       2.0 * M * N * K * batch):
         call("prifit_gemm_f32", layout, M, N, K, ptr(A), _LL(lda), _LL(sA), ptr(B), _LL(ldb), _LL(sB), ptr(C),
              _LL(ldc), _LL(sC), batch, splitk,
              ptr(a_affine[0]) if a_affine else None, ptr(a_affine[1]) if a_affine else None,
@@ -140,22 +144,245 @@ def _weight_grad(dY, P, Cout, Ain, Kin, a_affine, out=None):
     return dW
 
 
-def _fused_bwd(P, Cout, Kin, G, Y, scale, shift, ca, cb, cd, arg, Ttab, pool_K, W, Yp, aff_p, stats_p, dW, dev, red):
-    """Gp, the (m1, m2) sums of the layer below and dW of one layer in one pass (prifit_gemm_stream_bwd_f32).
-    red(Cp, ns_fn) -> (slab, fused_red): SharedMLPFn.backward's red_target."""
-    rslab, fused = red(Kin, lambda: query("prifit_gemm_stream_bwd_slabs", P, Cout, Kin))
+def _forward_kernel(last, pool_K, aligned, has_affine, P, Cout, Kin):
+    """The launch that forms a training-mode layer's product.  "stream_pool" / "tiled_pool": a max-pooled last layer whose epilogue
+    also emits (max, argmax, min, argmin) per 32 rows and column, so that the pool reads those candidates (1/8 of Y) instead
+    of Y -- on the streaming kernel, or on the tiled (persistent) one (SA2's 256-wide last layers).  "gemm": everything else."""
+    if last and pool_K and pool_K % 32 == 0 and _FUSE_POOL_FWD and aligned and has_affine:
+        if _stream_ok(NT, P, Cout, Kin):
+            return "stream_pool"
+        if query("prifit_gemm_pool_supported", P, Cout, Kin):
+            return "tiled_pool"
+    return "gemm"
+
+
+# How one layer of SharedMLPFn.backward gets from (G, its coefficients) to the gradient of the layer below.
+#   name    kernel                      what runs (DESIGN.md 3.1 has the entry points in order)
+#   pool    one_pass | pair             pooled last layer, dY = T*[k == arg] + b*Y + d formed inside its consumers from Y itself
+#   bn      one_pass | pair             middle layer, dY = a*(relu mask)*G + b*Y + d formed inside its consumers from G and Y
+#   norows  one_pass                    layer 2 over first-layer rows that were never stored
+#   direct0 rows | gather               first conv of a direct-mode set-abstraction scale: its weight gradient, dY formed on load
+#   gather0 csr | atomic                first layer by linearity: dU / dVc, dY formed on load
+#   preact0 None                        layer 0 is a pre-activation computed elsewhere: its dY is the gradient handed back
+#   plain   stream | tiled | gemm | None   dY written by an apply pass, then dW, then dA by the named kernel (None: not needed)
+# red: the route leaves the BatchNorm-backward (m1, m2) sums of the layer below, which then skips its own reduce pass.
+_Route = collections.namedtuple("_Route", "name kernel red")
+
+
+def _backward_route(l, L, P, Cout, Kin, pool_K, training, mode, need_dW, need_dx, g_dense, g_contig, below_ld4, N0=0):
+    """The route of layer l of an L-layer stack over P rows (Cout x Kin weights); launches nothing, reads the module switches
+    and query(...) only, at every call (tests flip the switches between two calls).
+    mode: how layer 0 comes about -- "plain" (a product like the others), "preact" (x is its pre-activation), "direct" /
+    "gather" (fused set-abstraction front end whose input gradients this function owns), "norows" (direct, rows not stored).
+    need_dW / need_dx: the layer's weight slot / the stack's input wants a gradient.  g_dense: G has row stride Cout and is
+    16-byte aligned; g_contig: G is contiguous; below_ld4: the row stride of the layer below is a multiple of 4; N0: points
+    per cloud (gather mode)."""
+    pooled = l == L - 1 and bool(pool_K)
+
+    def streams():   # both consumers of the layer's dY are streaming shapes
+        return _stream_ok(NN, P, Kin, Cout) and bool(query("prifit_gemm_stream_tn_supported", Cout, Kin, P))
+
+    # (groups of 64 rows: what the *_pool_f32 kernels take, against 32 in the forward epilogue; no 96-wide layer: kept as found)
+    if pooled and _FUSE_POOL and training and l > 0 and pool_K % 64 == 0 and Cout != 96 and need_dW and streams():
+        if (_fuse_bwd_on(Cout, Kin, True) and _FUSE_RED and query("prifit_gemm_stream_bwd_supported", P, Cout, Kin, pool_K) and
+                below_ld4):
+            return _Route("pool", "one_pass", True)
+        return _Route("pool", "pair", bool(_FUSE_RED))
+    if l == 0 and mode in ("direct", "norows"):
+        return _Route("direct0", "gather" if mode == "norows" else "rows", False)
+    if l == 0 and mode == "gather":
+        csr = _GATHER_BWD_CSR and query("prifit_gather_linear_bwd_csr_supported", N0, Cout) and g_contig
+        return _Route("gather0", "csr" if csr else "atomic", False)
+    fuse_bn = bool(_FUSE_BN_APPLY and _FUSE_RED and not pooled and training and l > 0 and need_dW and g_dense and streams())
+    if l == 1 and mode == "norows":
+        assert fuse_bn, "norows: the streaming backward of layer 2 is required (pointnet_util._norows_scales)"
+        return _Route("norows", "one_pass", True)
+    if fuse_bn:
+        if _fuse_bwd_on(Cout, Kin, False) and query("prifit_gemm_stream_bwd_supported", P, Cout, Kin, 0) and below_ld4:
+            return _Route("bn", "one_pass", True)
+        return _Route("bn", "pair", True)
+    if l == 0:
+        if mode == "preact":
+            return _Route("preact0", None, False)
+        return _Route("plain", "gemm" if need_dx else None, False)
+    if not _FUSE_RED:
+        return _Route("plain", "gemm", False)
+    return _Route("plain", "stream" if _stream_ok(NN, P, Kin, Cout) else "tiled", True)
+
+
+# The routes: f(ly, route) -> (G_prev, dW or None, the slab of sums left for the layer below or None, extra).  ly: the layer's
+# sizes, tensors and coefficients as SharedMLPFn.backward collects them (Yp, aff_p, stats_p: the rows, (scale, shift) and
+# (mean, invstd) of the layer below; dW: the layer's zero-filled [Cout, Kin] window of the stack's arena, None if not wanted).
+# extra: gather0's dVc; the plain route's dY.sum(0) where ly.want_db asks for it; None otherwise.
+
+def _fused_bwd(ly, route, Ttab=None):
+    """Gp, dW and the (m1, m2) sums of the layer below from one pass over the layer's rows: prifit_gemm_stream_bwd_f32 (Ttab:
+    the pooled layer, dY formed from the pool's table), or, on the norows route (the rows of the layer below were never stored),
+    prifit_gemm_stream_bwd_gather_f32, which re-forms them from U."""
+    P, Cout, Kin, G, Y, dev = ly.P, ly.Cout, ly.Kin, ly.G, ly.Y, ly.dev
+    rslab = torch.empty(query("prifit_gemm_stream_bwd_slabs", P, Cout, Kin), 2, Kin, dtype=torch.float32, device=dev)
     ws = torch.empty(query("prifit_gemm_stream_bwd_workspace", P, Cout, Kin), dtype=torch.float32, device=dev)
     Gp = torch.empty(P, Kin, dtype=torch.float32, device=dev)
-    (sc1, sh1), (mu1, is1) = aff_p, stats_p
-    pooled = arg is not None
+    (sc1, sh1), (mu1, is1) = ly.aff_p, ly.stats_p
+    pooled = Ttab is not None
+    if route.name == "norows":
+        nr = ly.front
+        with profiler.span(profiler.tag("gemm_stream_bwd", P, Cout, Kin, "gather"), 4.0 * P * (2 * Cout + Kin)):
+            call("prifit_gemm_stream_bwd_gather_f32", _LL(P), Cout, ptr(G), ptr(Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca),
+                 ptr(ly.cb), ptr(ly.cd), ptr(ly.W), _LL(Kin), ptr(nr["idx"]), ptr(nr["U"]), ptr(nr["Vc"]), nr["N"], nr["S"], nr["K"],
+                 ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(rslab), ptr(ly.dW), _LL(Kin), ptr(ws),
+                 cur_stream())
+        return Gp, ly.dW, rslab, None
     # HBM-bound on the narrow layers: every tensor once (G and Y or Y alone, Yp in, Gp out)
-    work = 4.0 * P * ((1 if pooled else 2) * Cout + 2 * Kin)
-    with profiler.span(profiler.tag("gemm_stream_bwd", P, Cout, Kin, "pool" if pooled else "bn"), work):
-        call("prifit_gemm_stream_bwd_f32", _LL(P), Cout, Kin, ptr(None if pooled else G), ptr(Y), ptr(None if pooled else scale),
-             ptr(None if pooled else shift), ptr(None if pooled else ca), ptr(cb), ptr(cd), ptr(arg), ptr(Ttab), int(pool_K or 0),
-             ptr(W), _LL(Kin), ptr(Yp), _LL(Yp.stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(rslab),
-             ptr(dW), _LL(Kin), ptr(ws), cur_stream())
-    return Gp, fused
+    with profiler.span(profiler.tag("gemm_stream_bwd", P, Cout, Kin, "pool" if pooled else "bn"),
+                       4.0 * P * ((1 if pooled else 2) * Cout + 2 * Kin)):
+        call("prifit_gemm_stream_bwd_f32", _LL(P), Cout, Kin, ptr(None if pooled else G), ptr(Y), ptr(None if pooled else ly.scale),
+             ptr(None if pooled else ly.shift), ptr(None if pooled else ly.ca), ptr(ly.cb), ptr(ly.cd),
+             ptr(ly.arg if pooled else None), ptr(Ttab), ly.pool_K if pooled else 0, ptr(ly.W), _LL(Kin), ptr(ly.Yp),
+             _LL(ly.Yp.stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(rslab), ptr(ly.dW), _LL(Kin),
+             ptr(ws), cur_stream())
+    return Gp, ly.dW, rslab, None
+
+
+def _route_pool(ly, route):
+    P, Cout, Kin, K, G, Y, W, Yp, dev = ly.P, ly.Cout, ly.Kin, ly.pool_K, ly.G, ly.Y, ly.W, ly.Yp, ly.dev
+    Ttab = torch.empty(P // K, Cout, dtype=torch.float32, device=dev)
+    call("prifit_pool_bwd_table", ptr(G), _LL(G.stride(0)), ptr(Y), _LL(Cout), ptr(ly.arg), ptr(ly.scale),
+         ptr(ly.shift), ptr(ly.ca), P // K, K, Cout, _F(0.0), ptr(Ttab), cur_stream())
+    if route.kernel == "one_pass":
+        return _fused_bwd(ly, route, Ttab)
+    ws = torch.empty(query("prifit_gemm_stream_tn_workspace", Cout, Kin, P), dtype=torch.float32, device=dev)
+    (sc1, sh1), (mu1, is1) = ly.aff_p, ly.stats_p
+    with profiler.span(profiler.tag("gemm_stream_tn", Cout, Kin, P, 1), 4.0 * P * (Cout + Kin)):
+        call("prifit_gemm_stream_tn_pool_f32", Cout, Kin, _LL(P), ptr(Y), _LL(Cout), ptr(Yp), _LL(Yp.stride(0)), ptr(ly.dW),
+             _LL(Kin), ptr(sc1), ptr(sh1), ptr(ly.arg), ptr(Ttab), ptr(ly.cb), ptr(ly.cd), K, ptr(ws), cur_stream())
+    G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
+    bias_dw = torch.mv(W.t(), ly.cd)   # the constant d^T W of every row of dY . W
+    rslab = None
+    if route.red:
+        rslab = torch.empty(query("prifit_gemm_stream_slabs", P, Cout), 2, Kin, dtype=torch.float32, device=dev)
+    with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, 1), 4.0 * (P * Cout + 2 * P * Kin + Kin * Cout)):
+        call("prifit_gemm_stream_dgrad_pool_f32", P, Kin, Cout, ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
+             _LL(Kin), ptr(bias_dw), ptr(ly.arg), ptr(Ttab), ptr(ly.cb), K, ptr(Yp), _LL(Yp.stride(0)),
+             ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
+    return G_prev, ly.dW, rslab, None
+
+
+def _route_bn(ly, route):
+    if route.kernel == "one_pass":
+        return _fused_bwd(ly, route)
+    P, Cout, Kin, G, Y, W, Yp, dev = ly.P, ly.Cout, ly.Kin, ly.G, ly.Y, ly.W, ly.Yp, ly.dev
+    ws = torch.empty(query("prifit_gemm_stream_tn_workspace", Cout, Kin, P), dtype=torch.float32, device=dev)
+    (sc1, sh1), (mu1, is1) = ly.aff_p, ly.stats_p
+    with profiler.span(profiler.tag("gemm_stream_tn", Cout, Kin, P, "bn"), 4.0 * P * (2 * Cout + Kin)):
+        call("prifit_gemm_stream_tn_bn_f32", Cout, Kin, _LL(P), ptr(G), ptr(Y), _LL(Cout), ptr(Yp), _LL(Yp.stride(0)),
+             ptr(ly.dW), _LL(Kin), ptr(sc1), ptr(sh1), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(ws),
+             cur_stream())
+    G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
+    rslab = torch.empty(query("prifit_gemm_stream_slabs", P, Cout), 2, Kin, dtype=torch.float32, device=dev)
+    with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, "bn"), 4.0 * (2 * P * Cout + 2 * P * Kin + Kin * Cout)):
+        call("prifit_gemm_stream_dgrad_bn_f32", P, Kin, Cout, ptr(G), ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
+             _LL(Kin), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(Yp), _LL(Yp.stride(0)),
+             ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
+    return G_prev, ly.dW, rslab, None
+
+
+def _route_direct0(ly, route):
+    """dW1 = dY^T [feat | rel] of a direct-mode set-abstraction scale's first conv, with dY formed on load."""
+    if not ly.need_dW:
+        return None, None, None, None
+    P, Cout, G, info, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
+    Bq, Nq, _ = info["xyz"].shape
+    Sq, Kq, Dq = info["new_xyz"].shape[1], info["K"], info["D"]
+    nblk = int(max(1, min(1024, (P + 1023) // 1024)))
+    part = torch.empty(nblk, Cout, Dq + 3, dtype=torch.float32, device=dev)
+    if route.kernel == "gather":
+        with profiler.span("sa_first_layer_dw", 4.0 * P * (Cout + 1)):
+            call("prifit_sa_first_layer_dw_bn_gather", ptr(G), ptr(info["U"]), ptr(info["Vc"]), ptr(ly.scale), ptr(ly.shift),
+                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]),
+                 ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout, Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
+    else:
+        with profiler.span("sa_first_layer_dw", 4.0 * P * (2 * Cout + 1)):
+            call("prifit_sa_first_layer_dw_bn", ptr(G), ptr(ly.Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd),
+                 ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]), ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout,
+                 Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
+    return None, slab_sum(part), None, None
+
+
+def _route_gather0(ly, route):
+    """dU / dVc of a first layer by linearity straight from (G, Y): BatchNorm + ReLU backward formed on load."""
+    P, Cout, G, info, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
+    Bq, Nq, Sq, Kq = info["B"], info["N"], info["S"], info["K"]
+    if route.kernel == "csr":
+        # as a gather over the in-edge lists of the points: no atomics, no staging, y1 re-formed from U / Vc (the
+        # layer's rows are not read); the CSR of the ball-query lists is built here, once per level and scale
+        Uq, Vq = info["U"].detach().contiguous(), info["Vc"].detach().contiguous()
+        E = Sq * Kq
+        offs = torch.empty(Bq, Nq + 1, dtype=torch.int32, device=dev)
+        lst, pos, own = (torch.empty(Bq, E, dtype=torch.int32, device=dev) for _ in range(3))
+        wsd = torch.empty(query("prifit_gather_linear_bwd_csr_workspace", Bq, Sq, Kq, Cout), dtype=torch.float64, device=dev)
+        dU = torch.empty(Bq, Nq, Cout, dtype=torch.float32, device=dev)
+        dVc = torch.empty(Bq, Sq, Cout, dtype=torch.float32, device=dev)
+        # bytes: G twice (once per pass), the lists, the tables
+        with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + 4.0 * P + 2.0 * (Bq * Nq + Bq * Sq) * Cout)):
+            call("prifit_list_csr", ptr(info["idx"]), Bq, Nq, E, ptr(offs), ptr(lst), ptr(pos), ptr(own), cur_stream())
+            call("prifit_gather_linear_bwd_csr", ptr(G), ptr(Uq), ptr(Vq), ptr(ly.bias0), ptr(ly.scale), ptr(ly.shift),
+                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(info["idx"]), ptr(offs), ptr(lst), ptr(own), Bq, Nq, Sq, Kq, Cout, ptr(dU),
+                 ptr(dVc), ptr(wsd), cur_stream())
+    else:
+        # the scatter staged in LDS, with atomics
+        dU = zero_pool.zeros(Bq, Nq, Cout, device=dev)
+        dVc = zero_pool.zeros(Bq, Sq, Cout, device=dev)
+        with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + P + (Bq * Nq + Bq * Sq) * Cout)):
+            call("prifit_gather_linear_bwd_bn", ptr(G), ptr(ly.Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd),
+                 ptr(info["idx"]), Bq, Nq, Sq, Kq, Cout, ptr(dU), ptr(dVc), cur_stream())
+    return None, dU, None, dVc
+
+
+def _route_plain(ly, route):
+    """dY written out by the layer's apply pass (preact0: that is all), then dW, then dA by route.kernel."""
+    P, Cout, Kin, G, W, Yp, dev = ly.P, ly.Cout, ly.Kin, ly.G, ly.W, ly.Yp, ly.dev
+    dY = torch.empty(P, Cout, dtype=torch.float32, device=dev)
+    if ly.pooled:
+        call("prifit_pool_bwd_apply", ptr(G), _LL(G.stride(0)), ptr(ly.Y), _LL(Cout), ptr(ly.arg), ptr(ly.scale), ptr(ly.shift),
+             ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), P // ly.pool_K, ly.pool_K, Cout, 0, _F(0.0), ptr(dY), _LL(Cout), cur_stream())
+    else:
+        call("prifit_bn_relu_bwd_apply", ptr(G), _LL(G.stride(0)), ptr(ly.Y), _LL(Cout), ptr(ly.scale), ptr(ly.shift),
+             ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), P, Cout, 0, _F(0.0), ptr(dY), _LL(Cout), cur_stream())
+    if route.name == "preact0":
+        return dY, None, None, None
+    dW = _weight_grad(dY, P, Cout, Yp, Kin, ly.aff_p, out=ly.dW) if ly.need_dW else None
+    db = dY.sum(dim=0) if ly.want_db else None
+    G_prev = None if route.kernel is None else torch.empty(P, Kin, dtype=torch.float32, device=dev)
+    rslab = None
+    if route.red:   # the dA product leaves the BatchNorm-backward column sums of the layer below: streaming or tiled kernel
+        (sc1, sh1), (mu1, is1) = ly.aff_p, ly.stats_p
+    if route.kernel == "gemm":
+        gemm(NN, P, Kin, Cout, dY, Cout, W, Kin, G_prev, Kin)
+    elif route.kernel == "stream":
+        rslab = torch.empty(query("prifit_gemm_stream_slabs", P, Cout), 2, Kin, dtype=torch.float32, device=dev)
+        with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, 0), 4.0 * (P * Cout + 2 * P * Kin + Kin * Cout)):
+            call("prifit_gemm_stream_dgrad_f32", P, Kin, Cout, ptr(dY), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
+                 _LL(Kin), ptr(Yp), _LL(Yp.stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
+    elif route.kernel == "tiled":
+        t = query("prifit_gemm_stats_tile_m", P, Kin)
+        rslab = torch.empty((P + t - 1) // t, 2, Kin, dtype=torch.float32, device=dev)
+        with profiler.span(profiler.tag("gemm_nn_bn%d" % _bn_tile(Kin), P, Kin, Cout, "red"), 2.0 * P * Kin * Cout):
+            call("prifit_gemm_dgrad_bnred_f32", P, Kin, Cout, ptr(dY), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
+                 _LL(Kin), ptr(Yp), _LL(Yp.stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
+    return G_prev, dW, rslab, db
+
+
+_ROUTES = {"pool": _route_pool, "bn": _route_bn, "norows": _fused_bwd, "direct0": _route_direct0,
+           "gather0": _route_gather0, "preact0": _route_plain, "plain": _route_plain}
+
+
+def _eval_coeffs(gamma, beta, rmean, rvar, eps):
+    """(scale, shift, mean, invstd) of an eval-mode BatchNorm, from its running statistics."""
+    invstd = torch.rsqrt(rvar + eps)
+    mean = rmean.clone()
+    scale = gamma * invstd
+    return scale, beta - mean * scale, mean, invstd
 
 
 class SharedMLPFn(torch.autograd.Function):
@@ -185,7 +412,6 @@ class SharedMLPFn(torch.autograd.Function):
             P, K0 = x.shape
             dev = x.device
         training = cfg["training"]
-        gather = cfg.get("preact_gather") if cfg.get("preact_slab") is not None else None
         Ys, affines, stats_saved, Ws = [], [], [], []
         prev, prev_aff = x, None
         cand = None
@@ -199,62 +425,44 @@ class SharedMLPFn(torch.autograd.Function):
                 Cout, Kin = W.shape
                 assert Kin == (nr["U"].shape[-1] if (l == 1 and nr is not None) else prev.shape[1]), (Kin, l)
                 Y = torch.empty(P, Cout, dtype=torch.float32, device=dev)
-            # training: the layer's coefficients [4, C] = scale, shift, mean, invstd, written by prifit_bn_finalize from the
-            # column-statistics slab of the launch that produces the layer
-            if training:
-                scale, shift, mean, invstd = torch.empty(4, Cout, dtype=torch.float32, device=dev).unbind(0)
-
-            def finalize(slab, nslab):
-                call("prifit_bn_finalize", ptr(slab), nslab, Cout, _D(float(P)), ptr(gamma), ptr(beta),
-                     _F(cfg["eps"]), _F(cfg["momentum"][l]), ptr(rmean), ptr(rvar), ptr(scale), ptr(shift),
-                     ptr(mean), ptr(invstd), cur_stream())
-
+            # slab: the column statistics of Y, written by the launch that produces the layer (training)
             if preact:
-                if training:
-                    finalize(cfg["preact_slab"], cfg["preact_slab"].shape[0])
-                else:
-                    invstd = torch.rsqrt(rvar + cfg["eps"])
-                    mean = rmean.clone()
-                    scale = gamma * invstd
-                    shift = beta - mean * scale
-            elif training and l == 1 and nr is not None:
+                slab = cfg["preact_slab"]
+            elif not training:
+                gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b)
+            elif l == 1 and nr is not None:
                 # layer 2 on rows that were never stored: the streaming product gathers them from U (prifit_gemm_stream_gather_f32)
-                nslab = query("prifit_gemm_stream_slabs", P, Kin)
-                slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
+                slab = torch.empty(query("prifit_gemm_stream_slabs", P, Kin), 2, Cout, dtype=torch.float32, device=dev)
                 with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, "gather"), 4.0 * (P * Cout + P + Cout * Kin)):
                     call("prifit_gemm_stream_gather_f32", P, Cout, ptr(nr["idx"]), ptr(nr["U"]), ptr(nr["Vc"]), nr["N"], nr["S"],
                          nr["K"], ptr(W), _LL(Kin), ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab),
                          cur_stream())
-                finalize(slab, nslab)
-            elif training:
+            else:
                 aligned = prev.stride(0) % 4 == 0 and prev.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
                 tile_m = query("prifit_gemm_stats_tile_m", P, Cout)
                 nslab = gemm_stats_slabs(P, Cout, Kin) if aligned else (P + tile_m - 1) // tile_m
                 slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
-                if (l == L - 1 and cfg["pool_K"] and cfg["pool_K"] % 32 == 0 and _FUSE_POOL_FWD and aligned and
-                        prev_aff is not None and _stream_ok(NT, P, Cout, Kin)):
-                    # max-pooled last layer on the streaming kernel: (max, argmax, min, argmin) per 32 rows and column come
-                    # out of the epilogue; the pool below reads those candidates (1/8 of Y) instead of Y
-                    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
-                    with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, 1), 4.0 * (P * Kin + P * Cout + Cout * Kin)):
-                        call("prifit_gemm_stream_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin),
-                             ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
-                elif (l == L - 1 and cfg["pool_K"] and cfg["pool_K"] % 32 == 0 and _FUSE_POOL_FWD and aligned and
-                        prev_aff is not None and not _stream_ok(NT, P, Cout, Kin) and query("prifit_gemm_pool_supported", P, Cout, Kin)):
-                    # the same on the tiled (persistent) kernel: SA2's 256-wide last layers
-                    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
-                    with profiler.span(profiler.tag("gemm_nt_bn128", P, Cout, Kin, "pool"), 2.0 * P * Cout * Kin):
-                        call("prifit_gemm_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin), ptr(Y),
-                             _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
-                else:
+                kernel = _forward_kernel(l == L - 1, cfg["pool_K"], aligned, prev_aff is not None, P, Cout, Kin)
+                if kernel == "gemm":
                     gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b, stats=slab)
-                finalize(slab, nslab)
+                else:
+                    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
+                    if kernel == "stream_pool":
+                        with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, 1), 4.0 * (P * Kin + P * Cout + Cout * Kin)):
+                            call("prifit_gemm_stream_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin),
+                                 ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
+                    else:
+                        with profiler.span(profiler.tag("gemm_nt_bn128", P, Cout, Kin, "pool"), 2.0 * P * Cout * Kin):
+                            call("prifit_gemm_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin), ptr(Y),
+                                 _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
+            if training:
+                # the layer's coefficients [4, C] = scale, shift, mean, invstd, written by prifit_bn_finalize from that slab
+                scale, shift, mean, invstd = torch.empty(4, Cout, dtype=torch.float32, device=dev).unbind(0)
+                call("prifit_bn_finalize", ptr(slab), slab.shape[0], Cout, _D(float(P)), ptr(gamma), ptr(beta),
+                     _F(cfg["eps"]), _F(cfg["momentum"][l]), ptr(rmean), ptr(rvar), ptr(scale), ptr(shift),
+                     ptr(mean), ptr(invstd), cur_stream())
             else:
-                gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b)
-                invstd = torch.rsqrt(rvar + cfg["eps"])
-                mean = rmean.clone()
-                scale = gamma * invstd
-                shift = beta - mean * scale
+                scale, shift, mean, invstd = _eval_coeffs(gamma, beta, rmean, rvar, cfg["eps"])
             Ys.append(Y)
             Ws.append(W)
             affines.append((scale, shift))
@@ -284,301 +492,91 @@ class SharedMLPFn(torch.autograd.Function):
             call("prifit_affine_relu", ptr(Ys[-1]), _LL(CL), ptr(prev_aff[0]), ptr(prev_aff[1]), P, CL, 0, _F(0.0),
                  ptr(out), _LL(CL), cur_stream())
         ctx.cfg = {k: v for k, v in cfg.items() if k not in ("preact_slab", "preact_direct", "preact_gather", "pool_out")}
-        ctx.preact_gather = gather
-        ctx.preact = cfg.get("preact_slab") is not None
-        # direct-mode set-abstraction front end: this function owns the gradient of the first conv's weight (tensors[0],
-        # upstream layout [C1, D+3]) and computes it with the BatchNorm backward fused in (prifit_sa_first_layer_dw_bn)
-        ctx.preact_direct = cfg.get("preact_direct") if ctx.preact else None
+        # how layer 0 came about (_backward_route's mode) and, for the fused set-abstraction front ends, whose input gradients
+        # backward owns, their record: direct (the first conv's weight, tensors[0] in upstream layout [C1, D+3]) or gather (U, Vc)
+        preact0 = cfg.get("preact_slab") is not None
+        direct = cfg.get("preact_direct") if preact0 else None
+        ctx.front = direct if direct is not None else (cfg.get("preact_gather") if preact0 else None)
+        if direct is not None:
+            ctx.mode = "norows" if direct.get("norows") else "direct"
+        else:
+            ctx.mode = "gather" if ctx.front is not None else ("preact" if preact0 else "plain")
         ctx.L = L
         ctx.P, ctx.dev = P, dev
         assert nr is None or (training and L >= 3 and Ys[0] is None)
         ctx.saved = (x, Ys, Ws, affines, stats_saved, arg)
-        ctx.biases = [tensors[6 * l + 1] for l in range(L)]
+        ctx.bias0 = tensors[1]
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        cfg, L = ctx.cfg, ctx.L
+        cfg, L, needs = ctx.cfg, ctx.L, ctx.needs_input_grad
         x, Ys, Ws, affines, stats_saved, arg = ctx.saved
-        training = cfg["training"]
-        P, dev = ctx.P, ctx.dev
-        nr = ctx.preact_direct if (ctx.preact_direct or {}).get("norows") else None
+        training, pool_K = cfg["training"], cfg["pool_K"]
+        P, dev, front, mode = ctx.P, ctx.dev, ctx.front, ctx.mode
         # a pooled stack takes its gradient with any row stride (a column slice of the concatenated multi-scale gradient:
         # every kernel that reads it has a leading dimension) -- no copy; the unpooled paths index rows densely
-        if not (cfg["pool_K"] and L > 1 and gout.dim() == 2 and gout.stride(1) == 1 and gout.stride(0) % 4 == 0 and
+        if not (pool_K and L > 1 and gout.dim() == 2 and gout.stride(1) == 1 and gout.stride(0) % 4 == 0 and
                 gout.data_ptr() % 16 == 0):
             gout = gout.contiguous()
         rps = _rows_per_slab()
         grads = [None] * (6 * L)
-        extra_grads = (None,) if ctx.preact_gather is not None else ()
         # one zero-filled arena for every weight gradient (split-K adds into it) and, in training, the (exactly
         # zero) bias gradients of this stack
         wslots, total = {}, 0
         for l in range(L):
             if Ws[l] is None:
                 continue
-            n = Ws[l].numel() if ctx.needs_input_grad[2 + 6 * l] else 0
-            nb = Ws[l].shape[0] if (training and ctx.needs_input_grad[2 + 6 * l + 1]) else 0
+            n = Ws[l].numel() if needs[2 + 6 * l] else 0
+            nb = Ws[l].shape[0] if (training and needs[2 + 6 * l + 1]) else 0
             wslots[l] = (total, n, total + n, nb)
             total += n + nb
         arena = zero_pool.zeros(total, device=dev) if total else None
         G_in = gout  # gradient w.r.t. the ReLU output of layer l (or pooled output for the last layer)
-        fused_red = None
+        fused_red = None   # the slab of (m1, m2) sums of layer l, where the route of the layer above has left it
         for l in range(L - 1, -1, -1):
             Y, W = Ys[l], Ws[l]
-            Cout, Kin = W.shape if W is not None else ((nr["U"].shape[-1] if Y is None else Y.shape[1]), 0)
+            Cout, Kin = W.shape if W is not None else ((front["U"].shape[-1] if Y is None else Y.shape[1]), 0)
             scale, shift = affines[l]
             mean, invstd = stats_saved[l]
-            pooled = (l == L - 1) and cfg["pool_K"]
+            pooled = l == L - 1 and bool(pool_K)
             # the layer's backward coefficients [5, C] = dgamma, dbeta, a, b, d (dY = a Gm + b Y + d): prifit_bn_bwd_finalize
-            # from the slab of (m1, m2) sums of the dA product of the layer above, or of the reduce pass below
+            # from the slab of (m1, m2) sums
             dgamma, dbeta, ca, cb, cd = torch.empty(5, Cout, dtype=torch.float32, device=dev).unbind(0)
-            # the pooled last layer: dY = T*[k == arg] + b*Y + d is formed inside the streaming dA / dW kernels from Y
-            # itself (no pool_bwd_apply pass writing dY, no reads of it) when both consumers are streaming shapes
-            fuse_pool = bool(pooled and _FUSE_POOL and training and l > 0 and W is not None and cfg["pool_K"] % 64 == 0 and Cout != 96 and
-                             ctx.needs_input_grad[2 + 6 * l] and _stream_ok(NN, P, Kin, Cout) and
-                             query("prifit_gemm_stream_tn_supported", Cout, Kin, P))
-            direct0 = l == 0 and ctx.preact_direct is not None
-            gather0 = l == 0 and ctx.preact_gather is not None
-            # a middle layer on streaming shapes: dY = a*(relu mask)*G + b*Y + d is formed inside its two consumers (the dW and
-            # the dA kernel read G and Y instead of dY: no bn_relu_bwd_apply pass writing dY, one read of it less)
-            fuse_bn = bool(_FUSE_BN_APPLY and _FUSE_RED and not pooled and not direct0 and training and l > 0 and W is not None and
-                           ctx.needs_input_grad[2 + 6 * l] and G_in.stride(0) == Cout and G_in.data_ptr() % 16 == 0 and
-                           _stream_ok(NN, P, Kin, Cout) and query("prifit_gemm_stream_tn_supported", Cout, Kin, P))
-            dY = None if (fuse_pool or direct0 or gather0 or fuse_bn) else torch.empty(P, Cout, dtype=torch.float32, device=dev)
             if pooled:
-                K = cfg["pool_K"]
-                G = P // K
                 prs = query("prifit_pool_reduce_groups_per_slab")
-                nslab = (G + prs - 1) // prs
-                slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
-                call("prifit_pool_bwd_reduce", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(arg),
-                     ptr(scale), ptr(shift), ptr(mean), ptr(invstd), G, K, Cout, 0, _F(0.0), ptr(slab), cur_stream())
+                slab = torch.empty((P // pool_K + prs - 1) // prs, 2, Cout, dtype=torch.float32, device=dev)
+                call("prifit_pool_bwd_reduce", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(arg), ptr(scale),
+                     ptr(shift), ptr(mean), ptr(invstd), P // pool_K, pool_K, Cout, 0, _F(0.0), ptr(slab), cur_stream())
             elif fused_red is not None:
-                slab, nslab = fused_red   # emitted by the dA product of the layer above (prifit_gemm_stream_dgrad_f32)
+                slab = fused_red
             else:
-                nslab = (P + rps - 1) // rps
-                slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
+                slab = torch.empty((P + rps - 1) // rps, 2, Cout, dtype=torch.float32, device=dev)
                 call("prifit_bn_relu_bwd_reduce", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(scale),
                      ptr(shift), ptr(mean), ptr(invstd), P, Cout, 0, _F(0.0), ptr(slab), cur_stream())
-            fused_red = None
-            call("prifit_bn_bwd_finalize", ptr(slab), nslab, Cout, _D(float(P)), int(training), ptr(scale),
+            call("prifit_bn_bwd_finalize", ptr(slab), slab.shape[0], Cout, _D(float(P)), int(training), ptr(scale),
                  ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta), ptr(ca), ptr(cb), ptr(cd), cur_stream())
-
-            def red_target(Cp, ns_fn):
-                """Where a dA product of this layer leaves the (m1, m2) sums of the layer below (Cp channels): -> (slab, the
-                `fused_red` value of the next iteration)."""
-                ns = ns_fn()
-                rs = torch.empty(ns, 2, Cp, dtype=torch.float32, device=dev)
-                return rs, (rs, ns)
-
-            if fuse_pool:
-                Ttab = torch.empty(G, Cout, dtype=torch.float32, device=dev)
-                call("prifit_pool_bwd_table", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(arg), ptr(scale),
-                     ptr(shift), ptr(ca), G, K, Cout, _F(0.0), ptr(Ttab), cur_stream())
-                wo, wn, bo, bn_ = wslots[l]
-                dW = arena[wo:wo + wn].view(Cout, Kin)
-                if _fuse_bwd_on(Cout, Kin, True) and _FUSE_RED and query("prifit_gemm_stream_bwd_supported", P, Cout, Kin, K) and Ys[l - 1].stride(0) % 4 == 0:
-                    G_prev, fused_red = _fused_bwd(P, Cout, Kin, None, Y, None, None, None, cb, cd, arg, Ttab, K, W, Ys[l - 1],
-                                                   affines[l - 1], stats_saved[l - 1], dW, dev, red_target)
-                    grads[6 * l] = dW
-                    if ctx.needs_input_grad[2 + 6 * l + 1]:
-                        grads[6 * l + 1] = arena[bo:bo + bn_]
-                    grads[6 * l + 2] = dgamma
-                    grads[6 * l + 3] = dbeta
-                    G_in = G_prev
-                    continue
-                ws = torch.empty(query("prifit_gemm_stream_tn_workspace", Cout, Kin, P), dtype=torch.float32, device=dev)
-                a_aff = affines[l - 1]
-                with profiler.span(profiler.tag("gemm_stream_tn", Cout, Kin, P, 1), 4.0 * P * (Cout + Kin)):
-                    call("prifit_gemm_stream_tn_pool_f32", Cout, Kin, _LL(P), ptr(Y), _LL(Cout), ptr(Ys[l - 1]),
-                         _LL(Ys[l - 1].stride(0)), ptr(dW), _LL(Kin), ptr(a_aff[0]), ptr(a_aff[1]), ptr(arg), ptr(Ttab),
-                         ptr(cb), ptr(cd), K, ptr(ws), cur_stream())
-                grads[6 * l] = dW
-                if ctx.needs_input_grad[2 + 6 * l + 1]:
-                    grads[6 * l + 1] = arena[bo:bo + bn_]
-                grads[6 * l + 2] = dgamma
-                grads[6 * l + 3] = dbeta
-                G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
-                bias_dw = torch.mv(W.t(), cd)   # the constant d^T W of every row of dY . W
-                rslab = fused_next = None
-                if _FUSE_RED:
-                    rslab, fused_next = red_target(Kin, lambda: query("prifit_gemm_stream_slabs", P, Cout))
-                (sc1, sh1), (mu1, is1) = affines[l - 1], stats_saved[l - 1]
-                with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, 1), 4.0 * (P * Cout + 2 * P * Kin + Kin * Cout)):
-                    call("prifit_gemm_stream_dgrad_pool_f32", P, Kin, Cout, ptr(Y), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
-                         _LL(Kin), ptr(bias_dw), ptr(arg), ptr(Ttab), ptr(cb), K, ptr(Ys[l - 1]), _LL(Ys[l - 1].stride(0)),
-                         ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
-                fused_red = fused_next
-                G_in = G_prev
-                continue
-            if direct0:
-                # first layer of a direct-mode set-abstraction scale: dW1 = dY^T [feat | rel] with dY formed on load
-                info = ctx.preact_direct
-                grads[2] = dgamma
-                grads[3] = dbeta
-                if ctx.needs_input_grad[2]:
-                    Bq, Nq, _ = info["xyz"].shape
-                    Sq, Kq, Dq = info["new_xyz"].shape[1], info["K"], info["D"]
-                    nblk = int(max(1, min(1024, (P + 1023) // 1024)))
-                    part = torch.empty(nblk, Cout, Dq + 3, dtype=torch.float32, device=dev)
-                    if nr is not None:
-                        with profiler.span("sa_first_layer_dw", 4.0 * P * (Cout + 1)):
-                            call("prifit_sa_first_layer_dw_bn_gather", ptr(G_in), ptr(nr["U"]), ptr(nr["Vc"]), ptr(scale), ptr(shift),
-                                 ptr(ca), ptr(cb), ptr(cd), ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]),
-                                 ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout, Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
-                    else:
-                        with profiler.span("sa_first_layer_dw", 4.0 * P * (2 * Cout + 1)):
-                            call("prifit_sa_first_layer_dw_bn", ptr(G_in), ptr(Y), ptr(scale), ptr(shift), ptr(ca), ptr(cb), ptr(cd),
-                                 ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]), ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout,
-                                 Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
-                    grads[0] = slab_sum(part)
-                if ctx.needs_input_grad[3]:
-                    grads[1] = zero_pool.zeros(Cout, device=dev)  # bias in front of a batch-stat BatchNorm
-                G_in = None
-                break
-            if gather0:
-                # first layer by linearity: dU / dVc straight from (G, Y) -- BatchNorm + ReLU backward formed on load, the
-                # scatter staged in LDS (prifit_gather_linear_bwd_bn)
-                info = ctx.preact_gather
-                Bq, Nq, Sq, Kq = info["B"], info["N"], info["S"], info["K"]
-                grads[2] = dgamma
-                grads[3] = dbeta
-                if _GATHER_BWD_CSR and query("prifit_gather_linear_bwd_csr_supported", Nq, Cout) and G_in.is_contiguous():
-                    # as a gather over the in-edge lists of the points: no atomics, no staging, y1 re-formed from U / Vc (the
-                    # layer's rows are not read); the CSR of the ball-query lists is built here, once per level and scale
-                    Uq, Vq = info["U"].detach().contiguous(), info["Vc"].detach().contiguous()
-                    E = Sq * Kq
-                    offs = torch.empty(Bq, Nq + 1, dtype=torch.int32, device=dev)
-                    lst, pos, own = (torch.empty(Bq, E, dtype=torch.int32, device=dev) for _ in range(3))
-                    wsd = torch.empty(query("prifit_gather_linear_bwd_csr_workspace", Bq, Sq, Kq, Cout), dtype=torch.float64, device=dev)
-                    dU = torch.empty(Bq, Nq, Cout, dtype=torch.float32, device=dev)
-                    dVc = torch.empty(Bq, Sq, Cout, dtype=torch.float32, device=dev)
-                    # bytes: G twice (once per pass), the lists, the tables
-                    with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + 4.0 * P + 2.0 * (Bq * Nq + Bq * Sq) * Cout)):
-                        call("prifit_list_csr", ptr(info["idx"]), Bq, Nq, E, ptr(offs), ptr(lst), ptr(pos), ptr(own), cur_stream())
-                        call("prifit_gather_linear_bwd_csr", ptr(G_in), ptr(Uq), ptr(Vq), ptr(ctx.biases[0]), ptr(scale), ptr(shift),
-                             ptr(ca), ptr(cb), ptr(cd), ptr(info["idx"]), ptr(offs), ptr(lst), ptr(own), Bq, Nq, Sq, Kq, Cout, ptr(dU),
-                             ptr(dVc), ptr(wsd), cur_stream())
-                else:
-                    dU = zero_pool.zeros(Bq, Nq, Cout, device=dev)
-                    dVc = zero_pool.zeros(Bq, Sq, Cout, device=dev)
-                    with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + P + (Bq * Nq + Bq * Sq) * Cout)):
-                        call("prifit_gather_linear_bwd_bn", ptr(G_in), ptr(Y), ptr(scale), ptr(shift), ptr(ca), ptr(cb), ptr(cd),
-                             ptr(info["idx"]), Bq, Nq, Sq, Kq, Cout, ptr(dU), ptr(dVc), cur_stream())
-                grads[0] = dU
-                if ctx.needs_input_grad[3]:
-                    grads[1] = zero_pool.zeros(Cout, device=dev)   # bias in front of a batch-stat BatchNorm
-                extra_grads = (dVc,)
-                G_in = None
-                break
-            if l == 1 and nr is not None:
-                # layer 2 over rows that were never stored: dA + dW + the BatchNorm-backward sums of layer 1 in the one-pass
-                # kernel, which re-forms layer 1's pre-activations from U (prifit_gemm_stream_bwd_gather_f32)
-                assert fuse_bn, "norows: the streaming backward of layer 2 is required (pointnet_util._norows_scales)"
-                wo, wn, bo, bn_ = wslots[l]
-                dW = arena[wo:wo + wn].view(Cout, Kin)
-                rslab, fused_next = red_target(Kin, lambda: query("prifit_gemm_stream_bwd_slabs", P, Cout, Kin))
-                ws = torch.empty(query("prifit_gemm_stream_bwd_workspace", P, Cout, Kin), dtype=torch.float32, device=dev)
-                G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
-                (sc1, sh1), (mu1, is1) = affines[0], stats_saved[0]
-                with profiler.span(profiler.tag("gemm_stream_bwd", P, Cout, Kin, "gather"), 4.0 * P * (2 * Cout + Kin)):
-                    call("prifit_gemm_stream_bwd_gather_f32", _LL(P), Cout, ptr(G_in), ptr(Y), ptr(scale), ptr(shift), ptr(ca),
-                         ptr(cb), ptr(cd), ptr(W), _LL(Kin), ptr(nr["idx"]), ptr(nr["U"]), ptr(nr["Vc"]), nr["N"], nr["S"], nr["K"],
-                         ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(G_prev), _LL(Kin), ptr(rslab), ptr(dW), _LL(Kin), ptr(ws),
-                         cur_stream())
-                grads[6 * l] = dW
-                if ctx.needs_input_grad[2 + 6 * l + 1]:
-                    grads[6 * l + 1] = arena[bo:bo + bn_]   # bias in front of a batch-stat BatchNorm: zero gradient
-                grads[6 * l + 2] = dgamma
-                grads[6 * l + 3] = dbeta
-                fused_red = fused_next
-                G_in = G_prev
-                continue
-            if fuse_bn:
-                wo, wn, bo, bn_ = wslots[l]
-                dW = arena[wo:wo + wn].view(Cout, Kin)
-                if _fuse_bwd_on(Cout, Kin, False) and query("prifit_gemm_stream_bwd_supported", P, Cout, Kin, 0) and Ys[l - 1].stride(0) % 4 == 0:
-                    G_prev, fused_red = _fused_bwd(P, Cout, Kin, G_in, Y, scale, shift, ca, cb, cd, None, None, 0, W, Ys[l - 1],
-                                                   affines[l - 1], stats_saved[l - 1], dW, dev, red_target)
-                    grads[6 * l] = dW
-                    if ctx.needs_input_grad[2 + 6 * l + 1]:
-                        grads[6 * l + 1] = arena[bo:bo + bn_]   # bias in front of a batch-stat BatchNorm: zero gradient
-                    grads[6 * l + 2] = dgamma
-                    grads[6 * l + 3] = dbeta
-                    G_in = G_prev
-                    continue
-                ws = torch.empty(query("prifit_gemm_stream_tn_workspace", Cout, Kin, P), dtype=torch.float32, device=dev)
-                a_aff = affines[l - 1]
-                with profiler.span(profiler.tag("gemm_stream_tn", Cout, Kin, P, "bn"), 4.0 * P * (2 * Cout + Kin)):
-                    call("prifit_gemm_stream_tn_bn_f32", Cout, Kin, _LL(P), ptr(G_in), ptr(Y), _LL(Cout), ptr(Ys[l - 1]),
-                         _LL(Ys[l - 1].stride(0)), ptr(dW), _LL(Kin), ptr(a_aff[0]), ptr(a_aff[1]), ptr(scale), ptr(shift),
-                         ptr(ca), ptr(cb), ptr(cd), ptr(ws), cur_stream())
-                grads[6 * l] = dW
-                if ctx.needs_input_grad[2 + 6 * l + 1]:
-                    grads[6 * l + 1] = arena[bo:bo + bn_]   # bias in front of a batch-stat BatchNorm: zero gradient
-                grads[6 * l + 2] = dgamma
-                grads[6 * l + 3] = dbeta
-                G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
-                rslab, fused_next = red_target(Kin, lambda: query("prifit_gemm_stream_slabs", P, Cout))
-                (sc1, sh1), (mu1, is1) = affines[l - 1], stats_saved[l - 1]
-                with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, "bn"), 4.0 * (2 * P * Cout + 2 * P * Kin + Kin * Cout)):
-                    call("prifit_gemm_stream_dgrad_bn_f32", P, Kin, Cout, ptr(G_in), ptr(Y), _LL(Cout), ptr(W), _LL(Kin),
-                         ptr(G_prev), _LL(Kin), ptr(scale), ptr(shift), ptr(ca), ptr(cb), ptr(cd), ptr(Ys[l - 1]),
-                         _LL(Ys[l - 1].stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(rslab), cur_stream())
-                fused_red = fused_next
-                G_in = G_prev
-                continue
-            if pooled:
-                call("prifit_pool_bwd_apply", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(arg),
-                     ptr(scale), ptr(shift), ptr(ca), ptr(cb), ptr(cd), G, K, Cout, 0, _F(0.0), ptr(dY), _LL(Cout),
-                     cur_stream())
-            else:
-                call("prifit_bn_relu_bwd_apply", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(scale),
-                     ptr(shift), ptr(ca), ptr(cb), ptr(cd), P, Cout, 0, _F(0.0), ptr(dY), _LL(Cout), cur_stream())
+            route = _backward_route(
+                l, L, P, Cout, Kin, pool_K, training, mode, needs[2 + 6 * l], needs[0],
+                g_dense=G_in.stride(0) == Cout and G_in.data_ptr() % 16 == 0, g_contig=G_in.is_contiguous(),
+                below_ld4=l > 0 and Ys[l - 1] is not None and Ys[l - 1].stride(0) % 4 == 0,
+                N0=front["N"] if mode == "gather" else 0)
+            wo, wn, bo, nb = wslots.get(l, (0, 0, 0, 0))
+            Yp, aff_p, stats_p = (Ys[l - 1], affines[l - 1], stats_saved[l - 1]) if l > 0 else (x, None, None)
+            ly = types.SimpleNamespace(
+                P=P, Cout=Cout, Kin=Kin, dev=dev, pooled=pooled, pool_K=pool_K, arg=arg, G=G_in, Y=Y, W=W, scale=scale, shift=shift,
+                ca=ca, cb=cb, cd=cd, Yp=Yp, aff_p=aff_p, stats_p=stats_p, front=front, bias0=ctx.bias0,
+                dW=arena[wo:wo + wn].view(Cout, Kin) if wn else None, need_dW=needs[2 + 6 * l],
+                want_db=needs[3 + 6 * l] and not training)
+            G_in, grads[6 * l], fused_red, extra = _ROUTES[route.name](ly, route)
+            if needs[3 + 6 * l]:
+                # a bias in front of a batch-statistics BatchNorm has zero gradient (the arena's zeros; layer 0 of a fused front
+                # end has no arena window); with running statistics it is sum(dY)
+                grads[6 * l + 1] = (arena[bo:bo + nb] if training else extra) if l in wslots else zero_pool.zeros(Cout, device=dev)
             grads[6 * l + 2] = dgamma
             grads[6 * l + 3] = dbeta
-            if l == 0 and ctx.preact:
-                G_in = dY
-                break
-            A_in = x if l == 0 else Ys[l - 1]
-            a_aff = None if l == 0 else affines[l - 1]
-            wo, wn, bo, bn_ = wslots[l]
-            if ctx.needs_input_grad[2 + 6 * l]:
-                grads[6 * l] = _weight_grad(dY, P, Cout, A_in, Kin, a_aff, out=arena[wo:wo + wn].view(Cout, Kin))
-            if ctx.needs_input_grad[2 + 6 * l + 1]:
-                # bias in front of a batch-stat BatchNorm has zero gradient; with running stats it is sum(dY)
-                grads[6 * l + 1] = arena[bo:bo + bn_] if training else dY.sum(dim=0)
-            grads[6 * l + 2] = dgamma
-            grads[6 * l + 3] = dbeta
-            if l > 0 or ctx.needs_input_grad[0]:
-                G_prev = torch.empty(P, Kin, dtype=torch.float32, device=dev)
-                if l > 0 and _FUSE_RED and _stream_ok(NN, P, Kin, Cout):
-                    # streaming dA product with the BatchNorm-backward column sums of layer l-1 in its epilogue
-                    rslab, fused_next = red_target(Kin, lambda: query("prifit_gemm_stream_slabs", P, Cout))
-                    (sc1, sh1), (mu1, is1) = affines[l - 1], stats_saved[l - 1]
-                    with profiler.span(profiler.tag("gemm_stream_nn", P, Kin, Cout, 0), 4.0 * (P * Cout + 2 * P * Kin + Kin * Cout)):
-                        call("prifit_gemm_stream_dgrad_f32", P, Kin, Cout, ptr(dY), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
-                             _LL(Kin), ptr(Ys[l - 1]), _LL(Ys[l - 1].stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1),
-                             ptr(rslab), cur_stream())
-                    fused_red = fused_next
-                elif l > 0 and _FUSE_RED:
-                    # tiled kernel, same epilogue
-                    rslab, fused_next = red_target(Kin, lambda: (P + query("prifit_gemm_stats_tile_m", P, Kin) - 1) // query("prifit_gemm_stats_tile_m", P, Kin))
-                    (sc1, sh1), (mu1, is1) = affines[l - 1], stats_saved[l - 1]
-                    with profiler.span(profiler.tag("gemm_nn_bn%d" % (32 if Kin <= 32 else (64 if Kin <= 64 else (96 if Kin <= 96 else 128))),
-                                                    P, Kin, Cout, "red"), 2.0 * P * Kin * Cout):
-                        call("prifit_gemm_dgrad_bnred_f32", P, Kin, Cout, ptr(dY), _LL(Cout), ptr(W), _LL(Kin), ptr(G_prev),
-                             _LL(Kin), ptr(Ys[l - 1]), _LL(Ys[l - 1].stride(0)), ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1),
-                             ptr(rslab), cur_stream())
-                    fused_red = fused_next
-                else:
-                    gemm(NN, P, Kin, Cout, dY, Cout, W, Kin, G_prev, Kin)
-                G_in = G_prev
-            else:
-                G_in = None
-            del dY
-        return (G_in, None) + tuple(grads) + extra_grads
+        # (gather mode: layer 0 took the gather0 route, whose extra is the gradient of Vc, the tensor behind the 6 L layer tensors)
+        return (G_in, None) + tuple(grads) + ((extra,) if mode == "gather" else ())
 
 
 class GatherLinearFn(torch.autograd.Function):
