@@ -10,7 +10,9 @@ Differences that are deliberate and documented (SURVEY.md section 8a'):
   * internally activations are channels-last and input channels are zero-padded to multiples of 4
     (weights are re-packed on the fly; gradients flow back to the upstream-shaped parameters).
 """
+import collections
 import contextlib
+import ctypes
 import os
 import weakref
 
@@ -18,11 +20,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import nn_ops, ops
 from .. import arena as zero_pool
 from .._lib import call, cur_stream, ptr, query
-from ..nn_ops import (ConcatWindowsFn, FpRowsFn, GatherLinearFn, GroupGatherFn, LinearFn, SAGroupDirectFn, SAGroupGatherFn, SharedMLPFn,
-                      ThreeInterpolateFn, _sa_group_launch, sa_group_supported)
+from ..nn_ops import (ConcatWindowsFn, FpRowsFn, FrontEnd, GatherLinearFn, GroupGatherFn, LinearFn, SAGroupDirectFn, SAGroupGatherFn,
+                      SharedMLPFn, ThreeInterpolateFn, _mlp_tensors, _ptr_array, _sa_group_launch, front_end_args, sa_group_supported,
+                      sa_point_tables)
 
 
 # ------------------------------------------------------------------ functional surface (:19-107)
@@ -112,8 +115,6 @@ class PackAllFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, specs, *ws):
-        import ctypes
-        from ..nn_ops import _ptr_array
         ws = [w.contiguous() for w in ws]
         idx = [_col_index(cols, w.shape[1], w.device) for cols, w in zip(specs, ws)]
         outs = [torch.empty(w.shape[0], len(cols), dtype=torch.float32, device=w.device) for cols, w in zip(specs, ws)]
@@ -127,8 +128,6 @@ class PackAllFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gs):
-        import ctypes
-        from ..nn_ops import _ptr_array
         live = [i for i, g in enumerate(gs) if g is not None]
         gws = [None] * len(gs)
         if live:
@@ -161,7 +160,7 @@ class PackPlan:
     def lookup(self, w, cols):
         base = w._base if w._base is not None else w
         key = (id(base), cols)
-        hit = self.results.get(key)
+        hit = None if self.results is None else self.results.get(key)
         if hit is not None:
             return hit
         if key not in self.keys and isinstance(base, nn.Parameter) and len(self.sites) < _pack_max_jobs():
@@ -181,17 +180,19 @@ def _pack_max_jobs():
 
 @contextlib.contextmanager
 def pack_plan(net):
-    """Inside: `_pack_cols` serves the weights of `net` from one launch (see PackPlan)."""
+    """Inside: `_pack_cols` serves the weights of `net` from one launch (see PackPlan).  Re-entrant: a forward of `net` inside
+    its own forward (activation checkpointing, embed() inside forward) gets its own results and hands the outer ones back."""
     global _active_plan
     plan = _plans.get(net)
     if plan is None:
         plan = _plans[net] = PackPlan()
     outer, _active_plan = _active_plan, plan
+    outer_results = plan.results
     plan.begin()
     try:
         yield plan
     finally:
-        plan.results = None
+        plan.results = outer_results
         _active_plan = outer
 
 
@@ -213,21 +214,27 @@ def _pack_weight(conv, perm_slices, kp):
     return _pack_cols(w, cols + [-1] * (kp - len(cols)))
 
 
-def _mlp_tensors(convs, bns, first_weight):
-    ts = []
-    for i, (conv, bn) in enumerate(zip(convs, bns)):
-        w = first_weight if i == 0 else conv.weight.reshape(conv.weight.shape[0], -1)
-        ts += [w, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    return ts
-
-
 # The first layer of a set-abstraction MLP is computed by linearity (no grouped tensor) when the grouped row would
 # be wider than the layer's output; PRIFIT_SA_LINEARITY=0 keeps the gather + GEMM form for A/B measurements.
 _SA_LINEARITY = os.environ.get("PRIFIT_SA_LINEARITY", "1") != "0"
-
-
-def _use_linearity(conv, kp):
-    return _SA_LINEARITY and kp > conv.weight.shape[0]
+# Ball query + grouping + the first conv of every per-radius MLP in ONE launch (csrc/sa_group.hip);
+# PRIFIT_SA_FUSED=0 keeps the separate ball-query / gather / GEMM launches for A/B measurements.
+_SA_FUSED = os.environ.get("PRIFIT_SA_FUSED", "1") != "0"
+# direct mode in training: the first layer's BatchNorm backward is fused into its weight-gradient kernel (0: separate
+# bn_relu_bwd_apply pass + SAGroupDirectFn autograd, A/B)
+_DIRECT_FUSED_BWD = os.environ.get("PRIFIT_SA_DIRECT_FUSED_BWD", "1") != "0"
+# gather mode in training: dU / dVc of the first layer come out of ONE kernel with that layer's BatchNorm + ReLU backward
+# folded in and the scatter staged in LDS (0: bn_relu_bwd_apply pass + SAGroupGatherFn autograd with global atomics, A/B)
+_GATHER_FUSED_BWD = os.environ.get("PRIFIT_SA_GATHER_FUSED_BWD", "1") != "0"
+# Direct-mode levels (SA1) in training: the 64-wide first-layer rows of a scale are NOT stored when every consumer can
+# re-form them from the L2-resident per-point table U (first layer by linearity, bias folded in) -- the forward product of
+# layer 2, the one-pass backward of layer 2 and the first conv's weight-gradient reduction (nn_ops.SharedMLPFn, FrontEnd
+# mode "norows").  SA1 at B = 24: 0.6 GB less written and 1.8 GB less read per step (2.4 GB of the step's ~36 GB of HBM traffic).
+# MEASURED AND NOT THE DEFAULT: the grouping launches drop from 0.21 to 0.125 ms, but every consumer is SLOWER on
+# rows gathered from L2 than on rows streamed from HBM (forward product +6 us, one-pass backward +26 us, weight-gradient
+# reduction +22 us per scale): c2 10.09 -> 10.17 ms, c3 15.19 -> 15.30 ms on one box, alternating runs.  These kernels are
+# not limited by HBM bytes alone.  PRIFIT_SA_NOROWS=1 turns it on (both arms are tested).
+_SA_NOROWS = os.environ.get("PRIFIT_SA_NOROWS", "0") != "0"
 
 
 def _linearity_rows(feats, xyz, new_xyz, kp):
@@ -264,52 +271,10 @@ def _linearity_operands(conv, feats, xyz, new_xyz, kp, feat_first, fold_bias=Fal
     return U, Vc
 
 
-def _first_layer_by_linearity(conv, bn_training, feats, xyz, new_xyz, idx, kp, feat_first):
-    """conv1 over the grouped [features | rel_xyz] rows without materialising them: project every POINT
-    once (U), every CENTRE once (Vc), then gather C1-wide rows (GatherLinearFn).  Used when the grouped row
-    would be wider than the layer's output."""
-    U, Vc = _linearity_operands(conv, feats, xyz, new_xyz, kp, feat_first)
-    return GatherLinearFn.apply(U, Vc, conv.bias, idx, bn_training)
-
-
-# Ball query + grouping + the first conv of every per-radius MLP in ONE launch (csrc/sa_group.hip);
-# PRIFIT_SA_FUSED=0 keeps the separate ball-query / gather / GEMM launches for A/B measurements.
-_SA_FUSED = os.environ.get("PRIFIT_SA_FUSED", "1") != "0"
-# direct mode in training: the first layer's BatchNorm backward is fused into its weight-gradient kernel (0: separate
-# bn_relu_bwd_apply pass + SAGroupDirectFn autograd, A/B)
-_DIRECT_FUSED_BWD = os.environ.get("PRIFIT_SA_DIRECT_FUSED_BWD", "1") != "0"
-
-
-def _fused_mode(first_convs, feats, N, nsamples, kp):
-    """None (separate launches), "direct" (narrow data inputs: weights in registers) or "gather" (by linearity)."""
-    if not (_SA_FUSED and _SA_LINEARITY) or not sa_group_supported(N, nsamples, [c.weight.shape[0] for c in first_convs]):
-        return None
-    D = 0 if feats is None else feats.shape[-1]
-    if D in (0, 3, 6) and (feats is None or not feats.requires_grad):
-        return "direct"
-    if all(_use_linearity(c, kp) for c in first_convs):
-        return "gather"
-    return None
-
-
-# Direct-mode levels (SA1) in training: the 64-wide first-layer rows of a scale are NOT stored when every consumer can
-# re-form them from the L2-resident per-point table U (first layer by linearity, bias folded in) -- the forward product of
-# layer 2, the one-pass backward of layer 2 and the first conv's weight-gradient reduction (nn_ops.SharedMLPFn, cfg
-# "norows").  SA1 at B = 24: 0.6 GB less written and 1.8 GB less read per step (2.4 GB of the step's ~36 GB of HBM traffic).
-# MEASURED AND NOT THE DEFAULT (DESIGN 5g): the grouping launches drop from 0.21 to 0.125 ms, but every consumer is SLOWER on
-# rows gathered from L2 than on rows streamed from HBM (forward product +6 us, one-pass backward +26 us, weight-gradient
-# reduction +22 us per scale): c2 10.09 -> 10.17 ms, c3 15.19 -> 15.30 ms on one box, alternating runs.  These kernels are
-# not limited by HBM bytes alone.  PRIFIT_SA_NOROWS=1 turns it on (both arms are tested).
-_SA_NOROWS = os.environ.get("PRIFIT_SA_NOROWS", "0") != "0"
-
-
-def _norows_scales(mode, conv_blocks, training, B, S, nsamples):
-    """Per scale: can its first-layer rows stay unstored?  (64-wide first layer, whole 64-row tiles per centre, >= 3 layers,
-    the second layer on the streaming forward kernel and the one-pass backward kernel.)"""
-    from .._lib import dll
-    from .. import nn_ops
-    if not (_SA_NOROWS and mode == "direct" and training and _DIRECT_FUSED_BWD and nn_ops._FUSE_RED and nn_ops._FUSE_BN_APPLY and
-            nn_ops._STREAM):
+def _norows_scales(conv_blocks, B, S, nsamples):
+    """Per scale of a direct-mode level in training: can its first-layer rows stay unstored?  (64-wide first layer, whole
+    64-row tiles per centre, >= 3 layers, the second layer on the streaming forward kernel and the one-pass backward kernel.)"""
+    if not (_SA_NOROWS and nn_ops._FUSE_RED and nn_ops._FUSE_BN_APPLY and nn_ops._STREAM):
         return [False] * len(conv_blocks)
     out = []
     for convs, K in zip(conv_blocks, nsamples):
@@ -323,124 +288,143 @@ def _norows_scales(mode, conv_blocks, training, B, S, nsamples):
     return out
 
 
-def nn_ops_point_tables(first_convs, feats, xyz, new_xyz, feat_first):
-    """U_r [B,N,C_r] (bias folded in) and Vc_r [B,S,C_r] of every radius in one launch (prifit_sa_point_tables)."""
-    import ctypes
-    from .._lib import call, cur_stream, ptr
-    from ..nn_ops import _ptr_array
-    B, N, _ = xyz.shape
-    S = new_xyz.shape[1]
-    D = 0 if feats is None else feats.shape[-1]
-    R = len(first_convs)
-    Ws = [c.weight.detach().reshape(c.weight.shape[0], -1).contiguous() for c in first_convs]
-    bs = [None if c.bias is None else c.bias.detach().contiguous() for c in first_convs]
-    Us = [torch.empty(B, N, w.shape[0], dtype=torch.float32, device=xyz.device) for w in Ws]
-    Vcs = [torch.empty(B, S, w.shape[0], dtype=torch.float32, device=xyz.device) for w in Ws]
-    wd = (ctypes.c_int * R)(*[int(w.shape[0]) for w in Ws])
-    call("prifit_sa_point_tables", ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(None if feats is None else feats.contiguous()),
-         B, N, S, D, int(feat_first), R, wd, _ptr_array(Ws), _ptr_array(bs), _ptr_array(Us), _ptr_array(Vcs), cur_stream())
-    return Us, Vcs
+# How the first layers of a set-abstraction level come about (DESIGN.md 3.2 has the entry points in order).
+#   name             what runs                                                               FrontEnd.mode of a scale
+#   direct           one fused launch, narrow inputs, weights in registers (data for autograd)   "direct"
+#   norows           sa_point_tables + one fused launch in the by-linearity form (data)       "norows" where norows[i], else "direct"
+#   gather           U / Vc products + one fused launch (data; U / Vc stay differentiable)    "gather"
+#   direct_autograd  SAGroupDirectFn (eval mode, or PRIFIT_SA_DIRECT_FUSED_BWD=0)             "preact"
+#   gather_autograd  U / Vc products + SAGroupGatherFn                                        "preact"
+#   separate         ball query, then per scale GatherLinearFn where linearity[i] ("preact"), else grouped rows + product (no record)
+_LevelRoute = collections.namedtuple("_LevelRoute", "name norows linearity", defaults=(None, None))
 
 
-def _fused_first_layers_norows(first_convs, norows, feats, xyz, new_xyz, radii, nsamples, kp, feat_first):
-    """Direct-mode level in training with some scales' rows unstored: ONE launch in the by-linearity form for all scales
-    (y = U_j - Vc_g, U = [feat | xyz] W1^T + b per point, Vc = c W1x^T per centre: the index lists and the BatchNorm
-    statistics of every scale, rows only where `norows` is False).  The first conv's weight gradient stays the direct
-    reduction dW1 = dY1^T [feat | rel] (SharedMLPFn owns it), so U / Vc are plain data for autograd."""
-    D = 0 if feats is None else feats.shape[-1]
-    B, N, _ = xyz.shape
-    S = new_xyz.shape[1]
-    with torch.no_grad():
-        Us, Vcs = nn_ops_point_tables(first_convs, feats, xyz, new_xyz, feat_first)
-        Ys, slabs, idxs = _sa_group_launch(1, xyz, new_xyz, None, True, list(radii), list(nsamples),
-                                           [u.shape[-1] for u in Us], None, Us, Vcs, [None] * len(first_convs),
-                                           rows=[not nr for nr in norows])
-    out = []
-    for i in range(len(first_convs)):
-        info = {"idx": idxs[i], "xyz": xyz, "new_xyz": new_xyz, "feat": feats, "feat_first": feat_first, "K": nsamples[i], "D": D}
-        if norows[i]:
-            info.update(norows=True, U=Us[i], Vc=Vcs[i], P=B * S * nsamples[i], N=N, S=S)
-        out.append((Ys[i], slabs[i], info))
-    return out
-
-
-def _fused_first_layers(mode, first_convs, training, feats, xyz, new_xyz, radii, nsamples, kp, feat_first,
-                        fused_gather_bwd=False):
-    """-> per radius (Y1 [B*S*K, C1], column-statistics slab, info): `info` is None, or -- direct mode in training --
-    the dict SharedMLPFn needs to take over the first conv's weight gradient (cfg["preact_direct"]): Y1 is then plain
-    data for autograd and the BatchNorm backward of that layer is fused into the weight-gradient kernel."""
-    if mode == "direct" and training and _DIRECT_FUSED_BWD:
+def _level_route(conv_blocks, feats, training, B, N, S, nsamples, kp, allow_norows):
+    """The route of a level; launches nothing, reads the module switches and query(...) only, at every call (tests flip the
+    switches between two calls)."""
+    widths = [blk[0].weight.shape[0] for blk in conv_blocks]
+    linearity = [_SA_LINEARITY and kp > c for c in widths]       # the grouped row would be wider than the layer's output
+    if _SA_FUSED and _SA_LINEARITY and sa_group_supported(N, nsamples, widths):
         D = 0 if feats is None else feats.shape[-1]
+        if D in (0, 3, 6) and (feats is None or not feats.requires_grad):
+            if not (training and _DIRECT_FUSED_BWD):
+                return _LevelRoute("direct_autograd")
+            norows = _norows_scales(conv_blocks, B, S, nsamples) if allow_norows else [False]
+            return _LevelRoute("norows", norows) if any(norows) else _LevelRoute("direct")
+        if all(linearity):
+            own_bwd = (training and _GATHER_FUSED_BWD and all(len(blk) >= 2 for blk in conv_blocks) and
+                       all(query("prifit_gather_linear_bwd_bn_supported", N, c) for c in widths))
+            return _LevelRoute("gather" if own_bwd else "gather_autograd")
+    return _LevelRoute("separate", None, linearity)
+
+
+def _fused_front_end(route, first_convs, training, feats, xyz, new_xyz, radii, nsamples, kp, feat_first):
+    """The fused launch of a level (any route but "separate") -> (one FrontEnd per scale, their Y1 [B*S*K, C1]; None where
+    the rows are not stored).  On the routes "direct" / "norows" / "gather" the launch is plain data for autograd: the
+    SharedMLPFn that consumes Y1 owns the first layer's backward (its BatchNorm backward folded into the weight-gradient
+    or dU / dVc kernel); on the "_autograd" routes SAGroup*Fn do."""
+    B, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    D = 0 if feats is None else feats.shape[-1]
+    R, radii, nsamples = len(first_convs), list(radii), list(nsamples)
+    if route.name in ("direct_autograd", "gather_autograd"):
+        ts = []
+        if route.name == "direct_autograd":
+            for c in first_convs:
+                ts += [c.weight.reshape(c.weight.shape[0], -1), c.bias]
+            out = SAGroupDirectFn.apply(xyz, new_xyz, feats, (radii, nsamples, feat_first, training), *ts)
+        else:
+            tables = _linearity_rows(feats, xyz, new_xyz, kp)
+            for c in first_convs:
+                U, Vc = _linearity_operands(c, feats, xyz, new_xyz, kp, feat_first, tables=tables)
+                ts += [U, Vc, c.bias]
+            out = SAGroupGatherFn.apply(xyz, new_xyz, (radii, nsamples, training), *ts)
+        return [FrontEnd("preact", out[2 * i + 1]) for i in range(R)], list(out[0::2])
+    if route.name == "direct":
         with torch.no_grad():
             Ws = [c.weight.reshape(c.weight.shape[0], -1).contiguous() for c in first_convs]
             bs = [None if c.bias is None else c.bias.contiguous() for c in first_convs]
             fx = feats is not None and D == 3 and feats.data_ptr() == xyz.data_ptr()
-            Ys, slabs, idxs = _sa_group_launch(0, xyz, new_xyz, feats, feat_first, list(radii), list(nsamples),
+            Ys, slabs, idxs = _sa_group_launch(0, xyz, new_xyz, feats, feat_first, radii, nsamples,
                                                [w.shape[0] for w in Ws], Ws, None, None, bs, feat_xyz=fx)
-        return [(Ys[i], slabs[i], {"idx": idxs[i], "xyz": xyz, "new_xyz": new_xyz, "feat": feats, "feat_first": feat_first,
-                                   "K": nsamples[i], "D": D}) for i in range(len(first_convs))]
-    if mode == "gather" and training and fused_gather_bwd:
-        # first layer by linearity, training: U / Vc stay differentiable, the launch itself is data for autograd, and the
-        # SharedMLPFn that consumes Y1 returns dU / dVc with its first BatchNorm backward folded in (cfg["preact_gather"])
-        B, N, _ = xyz.shape
-        S = new_xyz.shape[1]
-        tables = _linearity_rows(feats, xyz, new_xyz, kp)
-        ops_ = [_linearity_operands(c, feats, xyz, new_xyz, kp, feat_first, tables=tables) for c in first_convs]
+        tabs = [(None, None)] * R
+    else:
+        # the by-linearity form of the launch: y = U_j - Vc_g with U = [feat | xyz] W1^T per point, Vc = c W1x^T per centre
+        if route.name == "norows":
+            # U / Vc are plain data with the bias folded into U (the first conv's weight gradient stays the direct
+            # reduction dW1 = dY1^T [feat | rel]); index lists and statistics of every scale, rows only where wanted
+            with torch.no_grad():
+                Us, Vcs = sa_point_tables(first_convs, feats, xyz, new_xyz, feat_first)
+            tabs = [(u, v) if nr else (None, None) for u, v, nr in zip(Us, Vcs, route.norows)]
+            bs, rows = [None] * R, [not nr for nr in route.norows]
+        else:
+            # U / Vc stay differentiable: SharedMLPFn returns dU / dVc
+            tables = _linearity_rows(feats, xyz, new_xyz, kp)
+            tabs = [_linearity_operands(c, feats, xyz, new_xyz, kp, feat_first, tables=tables) for c in first_convs]
+            Us = [u.detach().contiguous() for u, _ in tabs]
+            Vcs = [v.detach().contiguous() for _, v in tabs]
+            bs, rows = [None if c.bias is None else c.bias.detach().contiguous() for c in first_convs], None
         with torch.no_grad():
-            Us = [u.detach().contiguous() for u, _ in ops_]
-            Vcs = [v.detach().contiguous() for _, v in ops_]
-            bs = [None if c.bias is None else c.bias.detach().contiguous() for c in first_convs]
-            Ys, slabs, idxs = _sa_group_launch(1, xyz, new_xyz, None, True, list(radii), list(nsamples),
-                                               [u.shape[-1] for u in Us], None, Us, Vcs, bs)
-        return [(Ys[i], slabs[i], {"gather": True, "idx": idxs[i], "U": ops_[i][0], "Vc": ops_[i][1], "B": B, "N": N, "S": S,
-                                   "K": nsamples[i]}) for i in range(len(first_convs))]
-    if mode == "direct":
-        ts = []
-        for c in first_convs:
-            ts += [c.weight.reshape(c.weight.shape[0], -1), c.bias]
-        out = SAGroupDirectFn.apply(xyz, new_xyz, feats, (list(radii), list(nsamples), feat_first, training), *ts)
-    else:
-        ts = []
-        tables = _linearity_rows(feats, xyz, new_xyz, kp)
-        for c in first_convs:
-            U, Vc = _linearity_operands(c, feats, xyz, new_xyz, kp, feat_first, tables=tables)
-            ts += [U, Vc, c.bias]
-        out = SAGroupGatherFn.apply(xyz, new_xyz, (list(radii), list(nsamples), training), *ts)
-    return [(out[2 * i], out[2 * i + 1], None) for i in range(len(first_convs))]
+            Ys, slabs, idxs = _sa_group_launch(1, xyz, new_xyz, None, True, radii, nsamples,
+                                               [u.shape[-1] for u in Us], None, Us, Vcs, bs, rows=rows)
+    fronts = []
+    for i in range(R):
+        if route.name == "gather":
+            fronts.append(FrontEnd("gather", slabs[i], idxs[i], B, N, S, nsamples[i], D, U=tabs[i][0], Vc=tabs[i][1]))
+        else:
+            fronts.append(FrontEnd("direct" if tabs[i][0] is None else "norows", slabs[i], idxs[i], B, N, S, nsamples[i], D,
+                                   xyz, new_xyz, feats, feat_first, *tabs[i]))
+    return fronts, Ys
 
 
-def _mlp_tensors_preact(convs, bns, info=None):
-    """Layer 0 is already computed: its W / bias slots are None -- unless SharedMLPFn owns the gradients of the fused
-    front end's inputs: direct mode (`info` without "gather") the first conv's weight in the W slot; gather mode U in the
-    W slot, the conv's bias in the bias slot and Vc behind the layer tensors."""
-    if info is not None and info.get("gather"):
-        ts = _mlp_tensors(convs, bns, info["U"])
-        return ts + [info["Vc"]]
-    if info is not None:
-        return _mlp_tensors(convs, bns, convs[0].weight.reshape(convs[0].weight.shape[0], -1))
-    ts = _mlp_tensors(convs, bns, None)
-    ts[1] = None
-    return ts
-
-
-def _preact_cfg(cfg, slab, info):
-    cfg["preact_slab"] = slab
-    if info is not None and info.get("gather"):
-        cfg["preact_gather"] = info
-    else:
-        cfg["preact_direct"] = info
-    return cfg
-
-
-# gather mode in training: dU / dVc of the first layer come out of ONE kernel with that layer's BatchNorm + ReLU backward
-# folded in and the scatter staged in LDS (0: bn_relu_bwd_apply pass + SAGroupGatherFn autograd with global atomics, A/B)
-_GATHER_FUSED_BWD = os.environ.get("PRIFIT_SA_GATHER_FUSED_BWD", "1") != "0"
-
-
-def _gather_bwd_ok(mode, convs_per_scale, N):
-    from .._lib import dll
-    return (mode == "gather" and _GATHER_FUSED_BWD and all(len(c) >= 2 for c in convs_per_scale) and
-            all(query("prifit_gather_linear_bwd_bn_supported", N, c[0].weight.shape[0]) for c in convs_per_scale))
+def _sa_level(conv_blocks, bn_blocks, npoint, radii, nsamples, training, xyz, feats, fps_start, *, feat_first, rows_perm, concat,
+              allow_norows):
+    """One sampled set-abstraction level, channels-last: xyz [B,N,3], feats [B,N,D] or None -> (new_xyz [B,S,3], out [B,S,C']):
+    farthest-point sampling, then per scale the grouped [feat | rel_xyz] rows through its MLP and the max over each group.
+    What the two modules differ in, beside the number of scales:
+      feat_first    upstream's column order of the first conv: [features, rel_xyz] (MSG, :247) or [rel_xyz, features] (:131)
+      rows_perm     the column slices of the first conv's weight in the order of the internal grouped rows [features, rel_xyz]
+      concat        True: the scales' pooled outputs are concatenated -- on the fused routes they are written side by side into
+                    column windows of one buffer (ConcatWindowsFn, no copy), else torch.cat; False: the one scale's output is it
+      allow_norows  the "norows" route may be taken (the single-scale module has never been wired to it: kept as found)"""
+    B, N, _ = xyz.shape
+    S = npoint
+    D = 0 if feats is None else feats.shape[-1]
+    kp = _pad4(D + 3)
+    _, new_xyz = ops.farthest_point_sample(xyz, S, fps_start, return_xyz=True)
+    route = _level_route(conv_blocks, feats, training, B, N, S, nsamples, kp, allow_norows)
+    pooled = []
+    if route.name != "separate":
+        fronts, ys = _fused_front_end(route, [blk[0] for blk in conv_blocks], training, feats, xyz, new_xyz, radii, nsamples, kp,
+                                      feat_first)
+        if concat:
+            widths = [blk[-1].weight.shape[0] for blk in conv_blocks]
+            wide = torch.empty(B * S, sum(widths), dtype=torch.float32, device=xyz.device)
+        c0 = 0
+        for i, K in enumerate(nsamples):
+            cfg, ts = front_end_args(_mlp_cfg(bn_blocks[i], K, training), conv_blocks[i], bn_blocks[i], fronts[i])
+            if concat:
+                cfg["pool_out"] = wide[:, c0:c0 + widths[i]]
+                c0 += widths[i]
+            pooled.append(SharedMLPFn.apply(ys[i], cfg, *ts))
+        out = ConcatWindowsFn.apply(wide, *pooled) if concat else pooled[0]
+        return new_xyz, out.reshape(B, S, -1)
+    idxs = ops.ball_query_multi(list(radii), list(nsamples), xyz, new_xyz)  # one pass, all radii
+    for i, K in enumerate(nsamples):
+        convs, bns = conv_blocks[i], bn_blocks[i]
+        if route.linearity[i]:
+            # conv1 over the grouped rows without materialising them: project every POINT once (U), every CENTRE once (Vc),
+            # then gather C1-wide rows
+            U, Vc = _linearity_operands(convs[0], feats, xyz, new_xyz, kp, feat_first)
+            y1, slab = GatherLinearFn.apply(U, Vc, convs[0].bias, idxs[i], training)
+            cfg, ts = front_end_args(_mlp_cfg(bns, K, training), convs, bns, FrontEnd("preact", slab))
+            pooled.append(SharedMLPFn.apply(y1, cfg, *ts))
+            continue
+        rows = GroupGatherFn.apply(feats, xyz, new_xyz, idxs[i], 0, kp)
+        w0 = _pack_weight(convs[0], rows_perm, kp)
+        pooled.append(SharedMLPFn.apply(rows, _mlp_cfg(bns, K, training), *_mlp_tensors(convs, bns, w0)))
+    out = torch.cat(pooled, dim=-1) if concat else pooled[0]
+    return new_xyz, out.reshape(B, S, -1)
 
 
 _pending_counters = None   # list while a model forward batches the BatchNorm step counters, else None
@@ -514,42 +498,23 @@ class PointNetSetAbstraction(nn.Module):
 
     def forward_cl(self, xyz, feats, fps_start=None):
         """channels-last: xyz [B,N,3], feats [B,N,D] or None -> (new_xyz [B,S,3], out [B,S,C'])."""
+        if not self.group_all:
+            # internal rows are [features, rel_xyz, pad]; upstream order is [rel_xyz, features] (:131)
+            D = 0 if feats is None else feats.shape[-1]
+            return _sa_level([self.mlp_convs], [self.mlp_bns], self.npoint, [self.radius], [self.nsample], self.training, xyz,
+                             feats, fps_start, feat_first=False, rows_perm=[(3, 3 + D), (0, 3)], concat=False, allow_norows=False)
         B, N, _ = xyz.shape
         D = 0 if feats is None else feats.shape[-1]
         kp = _pad4(D + 3)
-        if self.group_all:
-            S, K = 1, N
-            new_xyz = torch.zeros(B, 1, 3, device=xyz.device, dtype=xyz.dtype)
-            parts = [xyz] + ([feats] if feats is not None else [])  # :154 order [xyz, features]
-            if kp > D + 3:
-                parts.append(_z(xyz, B, N, kp - D - 3))
-            rows = torch.cat(parts, dim=-1).reshape(B * N, kp)
-            w0 = _pack_weight(self.mlp_convs[0], [(0, D + 3)], kp)
-        else:
-            S, K = self.npoint, self.nsample
-            _, new_xyz = ops.farthest_point_sample(xyz, S, fps_start, return_xyz=True)
-            mode = _fused_mode([self.mlp_convs[0]], feats, N, [K], kp)
-            if mode is not None:
-                (y1, slab, info), = _fused_first_layers(mode, [self.mlp_convs[0]], self.training, feats, xyz, new_xyz,
-                                                        [self.radius], [K], kp, feat_first=False,
-                                                        fused_gather_bwd=_gather_bwd_ok(mode, [self.mlp_convs], N))
-                cfg = _preact_cfg(_mlp_cfg(self.mlp_bns, K, self.training), slab, info)
-                out = SharedMLPFn.apply(y1, cfg, *_mlp_tensors_preact(self.mlp_convs, self.mlp_bns, info))
-                return new_xyz, out.reshape(B, S, -1)
-            idx = ops.ball_query_multi([self.radius], [K], xyz, new_xyz)[0]
-            # rows = [features, rel_xyz, pad]; upstream order is [rel_xyz, features] (:131)
-            if _use_linearity(self.mlp_convs[0], kp):
-                y1, slab = _first_layer_by_linearity(self.mlp_convs[0], self.training, feats, xyz, new_xyz, idx, kp,
-                                                     feat_first=False)
-                cfg = _mlp_cfg(self.mlp_bns, K, self.training)
-                cfg["preact_slab"] = slab
-                out = SharedMLPFn.apply(y1, cfg, *_mlp_tensors_preact(self.mlp_convs, self.mlp_bns))
-                return new_xyz, out.reshape(B, S, -1)
-            rows = GroupGatherFn.apply(feats, xyz, new_xyz, idx, 0, kp)
-            w0 = _pack_weight(self.mlp_convs[0], [(3, 3 + D), (0, 3)], kp)
-        out = SharedMLPFn.apply(rows, _mlp_cfg(self.mlp_bns, K, self.training),
+        new_xyz = torch.zeros(B, 1, 3, device=xyz.device, dtype=xyz.dtype)
+        parts = [xyz] + ([feats] if feats is not None else [])  # :154 order [xyz, features]
+        if kp > D + 3:
+            parts.append(_z(xyz, B, N, kp - D - 3))
+        rows = torch.cat(parts, dim=-1).reshape(B * N, kp)
+        w0 = _pack_weight(self.mlp_convs[0], [(0, D + 3)], kp)
+        out = SharedMLPFn.apply(rows, _mlp_cfg(self.mlp_bns, N, self.training),
                                 *_mlp_tensors(self.mlp_convs, self.mlp_bns, w0))
-        return new_xyz, out.reshape(B, S, -1)
+        return new_xyz, out.reshape(B, 1, -1)
 
     def forward(self, xyz, points, fps_start=None):
         """xyz [B,3,N], points [B,D,N] -> (new_xyz [B,3,S], new_points [B,D',S])."""
@@ -577,48 +542,10 @@ class PointNetSetAbstractionMsg(nn.Module):
             self.bn_blocks.append(bns)
 
     def forward_cl(self, xyz, feats, fps_start=None):
-        B, N, _ = xyz.shape
-        S = self.npoint
         D = 0 if feats is None else feats.shape[-1]
-        kp = _pad4(D + 3)
-        _, new_xyz = ops.farthest_point_sample(xyz, S, fps_start, return_xyz=True)
-        pooled = []
-        firsts = [blk[0] for blk in self.conv_blocks]
-        mode = _fused_mode(firsts, feats, N, self.nsample_list, kp) if len(firsts) <= 4 else None
-        if mode is not None:
-            norows = _norows_scales(mode, self.conv_blocks, self.training, B, S, self.nsample_list)
-            if any(norows):
-                ys = _fused_first_layers_norows(firsts, norows, feats, xyz, new_xyz, self.radius_list, self.nsample_list, kp,
-                                                feat_first=True)
-            else:
-                ys = _fused_first_layers(mode, firsts, self.training, feats, xyz, new_xyz, self.radius_list,
-                                         self.nsample_list, kp, feat_first=True,
-                                         fused_gather_bwd=_gather_bwd_ok(mode, self.conv_blocks, N))
-            # the scales write their pooled columns side by side into the level's output (no torch.cat)
-            widths = [blk[-1].weight.shape[0] for blk in self.conv_blocks]
-            wide = torch.empty(B * S, sum(widths), dtype=torch.float32, device=xyz.device)
-            c0 = 0
-            for i, K in enumerate(self.nsample_list):
-                cfg = _preact_cfg(_mlp_cfg(self.bn_blocks[i], K, self.training), ys[i][1], ys[i][2])
-                cfg["pool_out"] = wide[:, c0:c0 + widths[i]]
-                c0 += widths[i]
-                pooled.append(SharedMLPFn.apply(ys[i][0], cfg, *_mlp_tensors_preact(self.conv_blocks[i], self.bn_blocks[i],
-                                                                                    ys[i][2])))
-            return new_xyz, ConcatWindowsFn.apply(wide, *pooled).reshape(B, S, -1)
-        idxs = ops.ball_query_multi(self.radius_list, self.nsample_list, xyz, new_xyz)  # one pass, all radii
-        for i, K in enumerate(self.nsample_list):
-            if _use_linearity(self.conv_blocks[i][0], kp):
-                y1, slab = _first_layer_by_linearity(self.conv_blocks[i][0], self.training, feats, xyz, new_xyz,
-                                                     idxs[i], kp, feat_first=True)
-                cfg = _mlp_cfg(self.bn_blocks[i], K, self.training)
-                cfg["preact_slab"] = slab
-                pooled.append(SharedMLPFn.apply(y1, cfg, *_mlp_tensors_preact(self.conv_blocks[i], self.bn_blocks[i])))
-                continue
-            rows = GroupGatherFn.apply(feats, xyz, new_xyz, idxs[i], 0, kp)  # [features, rel_xyz] (:247)
-            w0 = _pack_weight(self.conv_blocks[i][0], [(0, D + 3)], kp)
-            pooled.append(SharedMLPFn.apply(rows, _mlp_cfg(self.bn_blocks[i], K, self.training),
-                                            *_mlp_tensors(self.conv_blocks[i], self.bn_blocks[i], w0)))
-        return new_xyz, torch.cat(pooled, dim=-1).reshape(B, S, -1)
+        # internal rows are [features, rel_xyz, pad]: upstream's own order (:247)
+        return _sa_level(self.conv_blocks, self.bn_blocks, self.npoint, self.radius_list, self.nsample_list, self.training, xyz,
+                         feats, fps_start, feat_first=True, rows_perm=[(0, D + 3)], concat=True, allow_norows=True)
 
     def forward(self, xyz, points, fps_start=None):
         x = xyz.permute(0, 2, 1).contiguous()

@@ -229,7 +229,7 @@ def _fused_bwd(ly, route, Ttab=None):
         nr = ly.front
         with profiler.span(profiler.tag("gemm_stream_bwd", P, Cout, Kin, "gather"), 4.0 * P * (2 * Cout + Kin)):
             call("prifit_gemm_stream_bwd_gather_f32", _LL(P), Cout, ptr(G), ptr(Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca),
-                 ptr(ly.cb), ptr(ly.cd), ptr(ly.W), _LL(Kin), ptr(nr["idx"]), ptr(nr["U"]), ptr(nr["Vc"]), nr["N"], nr["S"], nr["K"],
+                 ptr(ly.cb), ptr(ly.cd), ptr(ly.W), _LL(Kin), ptr(nr.idx), ptr(nr.U), ptr(nr.Vc), nr.N, nr.S, nr.K,
                  ptr(sc1), ptr(sh1), ptr(mu1), ptr(is1), ptr(Gp), _LL(Kin), ptr(rslab), ptr(ly.dW), _LL(Kin), ptr(ws),
                  cur_stream())
         return Gp, ly.dW, rslab, None
@@ -291,32 +291,30 @@ def _route_direct0(ly, route):
     """dW1 = dY^T [feat | rel] of a direct-mode set-abstraction scale's first conv, with dY formed on load."""
     if not ly.need_dW:
         return None, None, None, None
-    P, Cout, G, info, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
-    Bq, Nq, _ = info["xyz"].shape
-    Sq, Kq, Dq = info["new_xyz"].shape[1], info["K"], info["D"]
+    P, Cout, G, fe, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
     nblk = int(max(1, min(1024, (P + 1023) // 1024)))
-    part = torch.empty(nblk, Cout, Dq + 3, dtype=torch.float32, device=dev)
+    part = torch.empty(nblk, Cout, fe.D + 3, dtype=torch.float32, device=dev)
     if route.kernel == "gather":
         with profiler.span("sa_first_layer_dw", 4.0 * P * (Cout + 1)):
-            call("prifit_sa_first_layer_dw_bn_gather", ptr(G), ptr(info["U"]), ptr(info["Vc"]), ptr(ly.scale), ptr(ly.shift),
-                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]),
-                 ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout, Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
+            call("prifit_sa_first_layer_dw_bn_gather", ptr(G), ptr(fe.U), ptr(fe.Vc), ptr(ly.scale), ptr(ly.shift),
+                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(fe.idx), ptr(fe.xyz), ptr(fe.new_xyz),
+                 ptr(fe.feat), fe.B, fe.N, fe.S, fe.K, Cout, fe.D, int(fe.feat_first), nblk, ptr(part), cur_stream())
     else:
         with profiler.span("sa_first_layer_dw", 4.0 * P * (2 * Cout + 1)):
             call("prifit_sa_first_layer_dw_bn", ptr(G), ptr(ly.Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd),
-                 ptr(info["idx"]), ptr(info["xyz"]), ptr(info["new_xyz"]), ptr(info["feat"]), Bq, Nq, Sq, Kq, Cout,
-                 Dq, int(info["feat_first"]), nblk, ptr(part), cur_stream())
+                 ptr(fe.idx), ptr(fe.xyz), ptr(fe.new_xyz), ptr(fe.feat), fe.B, fe.N, fe.S, fe.K, Cout,
+                 fe.D, int(fe.feat_first), nblk, ptr(part), cur_stream())
     return None, slab_sum(part), None, None
 
 
 def _route_gather0(ly, route):
     """dU / dVc of a first layer by linearity straight from (G, Y): BatchNorm + ReLU backward formed on load."""
-    P, Cout, G, info, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
-    Bq, Nq, Sq, Kq = info["B"], info["N"], info["S"], info["K"]
+    P, Cout, G, fe, dev = ly.P, ly.Cout, ly.G, ly.front, ly.dev
+    Bq, Nq, Sq, Kq = fe.B, fe.N, fe.S, fe.K
     if route.kernel == "csr":
         # as a gather over the in-edge lists of the points: no atomics, no staging, y1 re-formed from U / Vc (the
         # layer's rows are not read); the CSR of the ball-query lists is built here, once per level and scale
-        Uq, Vq = info["U"].detach().contiguous(), info["Vc"].detach().contiguous()
+        Uq, Vq = fe.U.detach().contiguous(), fe.Vc.detach().contiguous()
         E = Sq * Kq
         offs = torch.empty(Bq, Nq + 1, dtype=torch.int32, device=dev)
         lst, pos, own = (torch.empty(Bq, E, dtype=torch.int32, device=dev) for _ in range(3))
@@ -325,9 +323,9 @@ def _route_gather0(ly, route):
         dVc = torch.empty(Bq, Sq, Cout, dtype=torch.float32, device=dev)
         # bytes: G twice (once per pass), the lists, the tables
         with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + 4.0 * P + 2.0 * (Bq * Nq + Bq * Sq) * Cout)):
-            call("prifit_list_csr", ptr(info["idx"]), Bq, Nq, E, ptr(offs), ptr(lst), ptr(pos), ptr(own), cur_stream())
+            call("prifit_list_csr", ptr(fe.idx), Bq, Nq, E, ptr(offs), ptr(lst), ptr(pos), ptr(own), cur_stream())
             call("prifit_gather_linear_bwd_csr", ptr(G), ptr(Uq), ptr(Vq), ptr(ly.bias0), ptr(ly.scale), ptr(ly.shift),
-                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(info["idx"]), ptr(offs), ptr(lst), ptr(own), Bq, Nq, Sq, Kq, Cout, ptr(dU),
+                 ptr(ly.ca), ptr(ly.cb), ptr(ly.cd), ptr(fe.idx), ptr(offs), ptr(lst), ptr(own), Bq, Nq, Sq, Kq, Cout, ptr(dU),
                  ptr(dVc), ptr(wsd), cur_stream())
     else:
         # the scatter staged in LDS, with atomics
@@ -335,7 +333,7 @@ def _route_gather0(ly, route):
         dVc = zero_pool.zeros(Bq, Sq, Cout, device=dev)
         with profiler.span("gather_linear_bwd", 4.0 * (2.0 * P * Cout + P + (Bq * Nq + Bq * Sq) * Cout)):
             call("prifit_gather_linear_bwd_bn", ptr(G), ptr(ly.Y), ptr(ly.scale), ptr(ly.shift), ptr(ly.ca), ptr(ly.cb), ptr(ly.cd),
-                 ptr(info["idx"]), Bq, Nq, Sq, Kq, Cout, ptr(dU), ptr(dVc), cur_stream())
+                 ptr(fe.idx), Bq, Nq, Sq, Kq, Cout, ptr(dU), ptr(dVc), cur_stream())
     return None, dU, None, dVc
 
 
@@ -385,29 +383,73 @@ def _eval_coeffs(gamma, beta, rmean, rvar, eps):
     return scale, beta - mean * scale, mean, invstd
 
 
+# How layer 0 of a shared-MLP stack came about when something else computed it: the record a set-abstraction front end
+# (models/pointnet_util._sa_level) hands to SharedMLPFn as cfg["front"].  No record: layer 0 is a product like the others
+# (_backward_route's mode "plain").  Fields a mode does not use are None.
+#   mode     "preact": x is layer 0's pre-activation and its gradient is handed back (GatherLinearFn, SAGroup*Fn autograd);
+#            "direct" / "gather": fused front end, x is plain data and SharedMLPFn owns the gradients of its inputs;
+#            "norows": direct, and the rows are not even stored (x is None): their consumers re-form them from (idx, U, Vc)
+#   slab     [nslab, 2, C] column statistics of x, written by the launch that produced it (read in training only: True
+#            does in eval mode)
+#   idx      int32 [B, S, K] ball-query lists;  B, N, S, K, D: clouds, points per cloud, centres, samples, feature width
+#   xyz, new_xyz, feat, feat_first    what the direct-mode weight gradient dW1 = dY^T [feat | rel] gathers from
+#   U, Vc    per-point / per-centre tables of the first layer by linearity (gather: differentiable; norows: data)
+FrontEnd = collections.namedtuple("FrontEnd", "mode slab idx B N S K D xyz new_xyz feat feat_first U Vc",
+                                  defaults=(None,) * 12)
+
+
+def _mlp_tensors(convs, bns, first_weight):
+    ts = []
+    for i, (conv, bn) in enumerate(zip(convs, bns)):
+        w = first_weight if i == 0 else conv.weight.reshape(conv.weight.shape[0], -1)
+        ts += [w, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
+    return ts
+
+
+def front_end_args(cfg, convs, bns, front):
+    """(cfg, tensors) of SharedMLPFn.apply(x, cfg, *tensors) for a stack whose layer 0 is described by `front` (a FrontEnd);
+    cfg: the stack's base dict (pool_K, training, eps, momentum), which gains "front".  Layer 0 has no product, so its two
+    weight slots carry what backward returns gradients for -- the one statement of that convention:
+      mode               tensors[0] (W slot)                     tensors[1] (bias slot)   behind the 6 L layer tensors
+      "preact"           None                                    None                     -
+      "direct", "norows" first conv's weight, upstream [C1, D+3] the conv's bias          -
+      "gather"           front.U                                 the conv's bias          front.Vc
+    (the bias of a fused front end gets the zero gradient of a bias in front of batch statistics; the gather mode's csr
+    backward re-forms y1 = U - Vc + bias from it)."""
+    cfg["front"] = front
+    if front.mode == "gather":
+        return cfg, _mlp_tensors(convs, bns, front.U) + [front.Vc]
+    if front.mode in ("direct", "norows"):
+        return cfg, _mlp_tensors(convs, bns, convs[0].weight.reshape(convs[0].weight.shape[0], -1))
+    ts = _mlp_tensors(convs, bns, None)
+    ts[1] = None
+    return cfg, ts
+
+
 class SharedMLPFn(torch.autograd.Function):
     """(conv1x1 + BatchNorm + ReLU) x L [+ max over the K samples of each group].
 
     apply(x, cfg, *tensors) with, per layer, tensors = (W [Cout, Kin], bias, gamma, beta,
-    running_mean, running_var); cfg = dict(pool_K, training, eps, momentum[list]).
+    running_mean, running_var); cfg = dict(pool_K, training, eps, momentum[list]) [+ pool_out, a column window the pooled
+    output is written into].
 
-    cfg["preact_slab"] (a [nslab, 2, C] column-statistics slab, or True in eval mode) marks x as the
-    already-computed pre-activation of layer 0 (GatherLinearFn): layer 0 then has no GEMM and its W/bias slots
-    are None; the gradient returned for x is the one w.r.t. that pre-activation.
-    cfg["preact_direct"] / cfg["preact_gather"] (training, fused set-abstraction front end): x is plain data and this
-    function owns the gradients of the front end's inputs -- direct: the first conv's weight sits in layer 0's W slot;
-    gather (first layer by linearity): U sits in layer 0's W slot, the conv's bias in its bias slot and Vc is appended
-    behind the 6 L layer tensors; their gradients come out of prifit_gather_linear_bwd_bn with the BatchNorm + ReLU
-    backward of layer 0 folded in (no dY of that layer is ever written)."""
+    cfg["front"] (a FrontEnd, built with front_end_args) says that layer 0 was computed elsewhere: it then has no GEMM, x is
+    its pre-activation (None in mode "norows") and front.slab its column statistics.  Mode "preact": the gradient returned
+    for x is the one w.r.t. that pre-activation.  Modes "direct" / "norows" / "gather" (training, fused set-abstraction
+    front end): x is plain data and this function returns the gradients of the front end's inputs from layer 0's slots (the
+    table at front_end_args), with the BatchNorm + ReLU backward of layer 0 folded into their kernels (no dY of that layer
+    is ever written)."""
 
     @staticmethod
     def forward(ctx, x, cfg, *tensors):
         L = len(tensors) // 6
+        front = cfg.get("front")
+        mode = "plain" if front is None else front.mode
         # norows: layer 0's pre-activation rows are not stored (x is None); they are re-formed from (idx, U, Vc) by the
-        # three kernels that consume them (cfg["preact_direct"]: norows, U, Vc, idx, P, N, S, K -- pointnet_util)
-        nr = cfg.get("preact_direct") if (cfg.get("preact_direct") or {}).get("norows") else None
+        # three kernels that consume them
+        nr = front if mode == "norows" else None
         if nr is not None:
-            P, dev = nr["P"], nr["U"].device
+            P, dev = nr.B * nr.S * nr.K, nr.U.device
         else:
             P, K0 = x.shape
             dev = x.device
@@ -417,25 +459,25 @@ class SharedMLPFn(torch.autograd.Function):
         cand = None
         for l in range(L):
             W, b, gamma, beta, rmean, rvar = tensors[6 * l:6 * l + 6]
-            preact = l == 0 and cfg.get("preact_slab") is not None
+            preact = l == 0 and front is not None
             if preact:
-                W, Cout, Kin, Y = None, (nr["U"].shape[-1] if nr is not None else x.shape[1]), 0, x
+                W, Cout, Kin, Y = None, (nr.U.shape[-1] if nr is not None else x.shape[1]), 0, x
             else:
                 W = W.contiguous()
                 Cout, Kin = W.shape
-                assert Kin == (nr["U"].shape[-1] if (l == 1 and nr is not None) else prev.shape[1]), (Kin, l)
+                assert Kin == (nr.U.shape[-1] if (l == 1 and nr is not None) else prev.shape[1]), (Kin, l)
                 Y = torch.empty(P, Cout, dtype=torch.float32, device=dev)
             # slab: the column statistics of Y, written by the launch that produces the layer (training)
             if preact:
-                slab = cfg["preact_slab"]
+                slab = front.slab
             elif not training:
                 gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b)
             elif l == 1 and nr is not None:
                 # layer 2 on rows that were never stored: the streaming product gathers them from U (prifit_gemm_stream_gather_f32)
                 slab = torch.empty(query("prifit_gemm_stream_slabs", P, Kin), 2, Cout, dtype=torch.float32, device=dev)
                 with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, "gather"), 4.0 * (P * Cout + P + Cout * Kin)):
-                    call("prifit_gemm_stream_gather_f32", P, Cout, ptr(nr["idx"]), ptr(nr["U"]), ptr(nr["Vc"]), nr["N"], nr["S"],
-                         nr["K"], ptr(W), _LL(Kin), ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab),
+                    call("prifit_gemm_stream_gather_f32", P, Cout, ptr(nr.idx), ptr(nr.U), ptr(nr.Vc), nr.N, nr.S,
+                         nr.K, ptr(W), _LL(Kin), ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab),
                          cur_stream())
             else:
                 aligned = prev.stride(0) % 4 == 0 and prev.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
@@ -491,16 +533,9 @@ class SharedMLPFn(torch.autograd.Function):
             out = torch.empty(P, CL, dtype=torch.float32, device=dev)
             call("prifit_affine_relu", ptr(Ys[-1]), _LL(CL), ptr(prev_aff[0]), ptr(prev_aff[1]), P, CL, 0, _F(0.0),
                  ptr(out), _LL(CL), cur_stream())
-        ctx.cfg = {k: v for k, v in cfg.items() if k not in ("preact_slab", "preact_direct", "preact_gather", "pool_out")}
-        # how layer 0 came about (_backward_route's mode) and, for the fused set-abstraction front ends, whose input gradients
-        # backward owns, their record: direct (the first conv's weight, tensors[0] in upstream layout [C1, D+3]) or gather (U, Vc)
-        preact0 = cfg.get("preact_slab") is not None
-        direct = cfg.get("preact_direct") if preact0 else None
-        ctx.front = direct if direct is not None else (cfg.get("preact_gather") if preact0 else None)
-        if direct is not None:
-            ctx.mode = "norows" if direct.get("norows") else "direct"
-        else:
-            ctx.mode = "gather" if ctx.front is not None else ("preact" if preact0 else "plain")
+        ctx.cfg = {k: v for k, v in cfg.items() if k not in ("front", "pool_out")}
+        # how layer 0 came about (_backward_route's mode) and the front end's record (the fused modes read it in backward)
+        ctx.mode, ctx.front = mode, front
         ctx.L = L
         ctx.P, ctx.dev = P, dev
         assert nr is None or (training and L >= 3 and Ys[0] is None)
@@ -536,7 +571,7 @@ class SharedMLPFn(torch.autograd.Function):
         fused_red = None   # the slab of (m1, m2) sums of layer l, where the route of the layer above has left it
         for l in range(L - 1, -1, -1):
             Y, W = Ys[l], Ws[l]
-            Cout, Kin = W.shape if W is not None else ((front["U"].shape[-1] if Y is None else Y.shape[1]), 0)
+            Cout, Kin = W.shape if W is not None else ((front.U.shape[-1] if Y is None else Y.shape[1]), 0)
             scale, shift = affines[l]
             mean, invstd = stats_saved[l]
             pooled = l == L - 1 and bool(pool_K)
@@ -560,7 +595,7 @@ class SharedMLPFn(torch.autograd.Function):
                 l, L, P, Cout, Kin, pool_K, training, mode, needs[2 + 6 * l], needs[0],
                 g_dense=G_in.stride(0) == Cout and G_in.data_ptr() % 16 == 0, g_contig=G_in.is_contiguous(),
                 below_ld4=l > 0 and Ys[l - 1] is not None and Ys[l - 1].stride(0) % 4 == 0,
-                N0=front["N"] if mode == "gather" else 0)
+                N0=front.N if mode == "gather" else 0)
             wo, wn, bo, nb = wslots.get(l, (0, 0, 0, 0))
             Yp, aff_p, stats_p = (Ys[l - 1], affines[l - 1], stats_saved[l - 1]) if l > 0 else (x, None, None)
             ly = types.SimpleNamespace(
@@ -663,6 +698,22 @@ def _sa_group_launch(mode, xyz, new_xyz, feat, feat_first, radii, nsamples, widt
              _ptr_array(Vcs) if Vcs else None, _ptr_array(biases), _ptr_array(Ys), _ptr_array(slabs), _ptr_array(idxs),
              cur_stream())
     return Ys, slabs, idxs
+
+
+def sa_point_tables(first_convs, feats, xyz, new_xyz, feat_first):
+    """U_r [B,N,C_r] (bias folded in) and Vc_r [B,S,C_r] of every radius in one launch (prifit_sa_point_tables)."""
+    B, N, _ = xyz.shape
+    S = new_xyz.shape[1]
+    D = 0 if feats is None else feats.shape[-1]
+    R = len(first_convs)
+    Ws = [c.weight.detach().reshape(c.weight.shape[0], -1).contiguous() for c in first_convs]
+    bs = [None if c.bias is None else c.bias.detach().contiguous() for c in first_convs]
+    Us = [torch.empty(B, N, w.shape[0], dtype=torch.float32, device=xyz.device) for w in Ws]
+    Vcs = [torch.empty(B, S, w.shape[0], dtype=torch.float32, device=xyz.device) for w in Ws]
+    wd = (ctypes.c_int * R)(*[int(w.shape[0]) for w in Ws])
+    call("prifit_sa_point_tables", ptr(xyz.contiguous()), ptr(new_xyz.contiguous()), ptr(None if feats is None else feats.contiguous()),
+         B, N, S, D, int(feat_first), R, wd, _ptr_array(Ws), _ptr_array(bs), _ptr_array(Us), _ptr_array(Vcs), cur_stream())
+    return Us, Vcs
 
 
 class SAGroupDirectFn(torch.autograd.Function):
