@@ -10,6 +10,8 @@ coefficient tables).  `get_model(num_part, normal_channel, k)` is the adapter th
 expects for `'dgcnn' in args.model` (train_partseg_shapenet.py:226-228) but never shipped.
 """
 import ctypes
+import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -24,22 +26,43 @@ from ..nn_ops import NN, NT, TN, LinearFn, gemm
 _LL = ctypes.c_longlong
 _F = ctypes.c_float
 _D = ctypes.c_double
+
+# The switches (A/B arms; which route each one selects: DESIGN 3.3).  The route functions read them at every call.
 # GroupNorm statistics -> coefficient tables in one launch each way (0: the torch fp64 form, ~35 tiny launches per layer; A/B)
-_GN_KERNELS = __import__("os").environ.get("PRIFIT_GN_KERNELS", "1") != "0"
+_GN_KERNELS = os.environ.get("PRIFIT_GN_KERNELS", "1") != "0"
 # bias / offset gradients of a convolution in front of a GroupNorm from the statistics (0: torch's column sums over dY; A/B arm, tested)
-_GN_COLSUMS = __import__("os").environ.get("PRIFIT_GN_COLSUMS", "1") != "0"
+_GN_COLSUMS = os.environ.get("PRIFIT_GN_COLSUMS", "1") != "0"
+# the first graph (C = 3) straight from the cloud, no [B,N,N] pairwise matrix (prifit_knn3_topk; 0: product + selection, A/B arm)
+_KNN3_FUSED = os.environ.get("PRIFIT_KNN3_FUSED", "1") != "0"
+# the pairwise matrix of a feature graph on the symmetric kernel (0: the general product; A/B arm, tested bit-equal)
+_KNN_GRAM_SYM = os.environ.get("PRIFIT_KNN_GRAM_SYM", "1") != "0"
+# The edge convolution by linearity (default): W [x_j - x_i | x_i] = Wa x_j + (Wb - Wa) x_i = U_j - Vc_i with U = X Wa^T and
+# Vc = X (Wa - Wb)^T computed once per POINT (two products over B N rows); per EDGE only a gather of Cout-wide rows of U
+# (nn_ops.GatherLinearFn, the kernel of the set-abstraction first layers).  The [B N k, 2C] edge rows of upstream
+# (src/dgcnn.py:98-105), the products over B N k rows (49 GFLOP forward at B = 24, k = 20) and their autograd (a dA and a dW
+# product over the edge rows, a 2C-wide scatter) never exist.  PRIFIT_EDGE_LINEARITY=0: rows + product (A/B arm; tested).
+_EDGE_LINEARITY = os.environ.get("PRIFIT_EDGE_LINEARITY", "1") != "0"
+# ... with its pooled GroupNorm backward formed inside the scatter (0: apply pass writes dY, then the scatter; A/B arm, tested)
+_EDGE_FUSED_BWD = os.environ.get("PRIFIT_EDGE_FUSED_BWD", "1") != "0"
+# ... and, by default, with no per-edge tensor at all (EdgeConvTabFn; 0: the pre-activations are written and re-read; A/B arm, tested)
+_EDGE_TABLES = os.environ.get("PRIFIT_EDGE_TABLES", "1") != "0"
+# the global max over the cloud fused into the mlp1 block (0: activation pass + torch max; A/B arm, tested)
+_GLOBAL_POOL_FUSED = os.environ.get("PRIFIT_GLOBAL_POOL_FUSED", "1") != "0"
+# ... and its backward in the algebraic form: no [B N, Cout] tensor dY, the two products over it replaced by per-sample
+# [Cin, Cin] products and B x Cout winners' rows (0: pool_bwd_apply + the dense dA / dW products; A/B arm, tested)
+_GLOBAL_POOL_ALG = os.environ.get("PRIFIT_GLOBAL_POOL_ALG", "1") != "0"
+# ... whose forward then does not store the product at all (0: stores it; A/B arm, tested)
+_GLOBAL_POOL_NOSTORE = os.environ.get("PRIFIT_GLOBAL_POOL_NOSTORE", "1") != "0"
 
 
 def _pad4(c):
     return (c + 3) // 4 * 4
 
 
-# the first graph (C = 3) straight from the cloud, no [B,N,N] pairwise matrix (prifit_knn3_topk; 0: product + selection, A/B arm)
-_KNN3_FUSED = __import__("os").environ.get("PRIFIT_KNN3_FUSED", "1") != "0"
-
-
-# the pairwise matrix of a feature graph on the symmetric kernel (0: the general product; A/B arm, tested bit-equal)
-_KNN_GRAM_SYM = __import__("os").environ.get("PRIFIT_KNN_GRAM_SYM", "1") != "0"
+def _pad_cols(t, ld):
+    """t [rows, C] with zero columns up to ld (16-byte rows for the product kernels).  torch.cat, as the linear and rows arms
+    of the edge convolution always padded; the tables arm keeps F.pad, whose autograd launches differ."""
+    return torch.cat([t, t.new_zeros(t.shape[0], ld - t.shape[1])], dim=1) if ld > t.shape[1] else t
 
 
 def _knn_cl(x, k):
@@ -182,23 +205,49 @@ def _gn_tables(slab, Bs, sps, Cout, rows, gamma, beta, cfg, offset=None, chsum=N
     return scale, shift, mean, invstd
 
 
-def _gn_forward(Y, slab, tile, gamma, beta, cfg, offset=None, cand=None, chsum=None, shape=None, ystar=None):
+# What a GroupNorm block keeps for its backward: the per-sample tables [Bs, C]; arg (pooled: the winners' rows); chsum (float64
+# column sums of Y per sample, for a bias / offset gradient); ystar (the winners' pre-activations where Y was not stored)
+GNState = namedtuple("GNState", "scale shift mean invstd arg chsum ystar")
+# The reduction half of the backward: dY = ca * act'(.) * gout + cb * Y + cd; with chsum also the column sums of dY per sample
+# (dsum [Bs, C]) and over all rows (db [C]); pooled over the whole cloud: gm [Bs, C] = act'(.) * gout at the winners
+GNGrads = namedtuple("GNGrads", "gout ca cb cd dgamma dbeta dsum db gm")
+
+
+def _save_gn(ctx, state, *tensors):
+    """The tables and arg through save_for_backward behind `tensors`; chsum and ystar as attributes (neither is an input or an
+    output of a node, so no reference cycle: the distinction is explained at fit_ops.MeanShiftFn)."""
+    ctx.save_for_backward(*tensors, *state[:5])
+    ctx.gn_attrs = state[5:]
+
+
+def _saved_gn(ctx, n):
+    return ctx.saved_tensors[:n], GNState(*ctx.saved_tensors[n:], *ctx.gn_attrs)
+
+
+def _gn_cfg(gn, rps, slope, pool_K=0):
+    return {"groups": gn.num_groups, "rps": rps, "slope": slope, "pool_K": pool_K, "eps": gn.eps}
+
+
+def _gn_forward(Y, slab, tile, gamma, beta, cfg, offset=None, cand=None, keep_chsum=False, shape=None):
     """GroupNorm statistics from the 128-row (or `tile`-row) column-statistics slabs of Y [P, C] -> per-sample coefficient
-    tables, then LeakyReLU [+ max over the pool_K rows of each group].  Returns (out, scale, shift, mean, invstd, arg).
+    tables, then LeakyReLU [+ max over the pool_K rows of each group].  Returns (out, GNState).
     offset [Bs, C] (optional): the normalised tensor is Y + offset[sample] (prifit_gn_finalize_offset: the tables come out
     relative to Y, so nothing downstream changes)."""
     P, Cout = shape if Y is None else Y.shape          # Y None: the product was not stored (candidates only; `shape` given)
-    G, rps, slope, pool_K, eps = cfg["groups"], cfg["rps"], cfg["slope"], cfg["pool_K"], cfg["eps"]
+    G, rps, slope, pool_K = cfg["groups"], cfg["rps"], cfg["slope"], cfg["pool_K"]
     assert P % rps == 0 and rps % tile == 0 and Cout % G == 0
     Bs = P // rps
     dev = slab.device
+    chsum = torch.empty(Bs, Cout, dtype=torch.float64, device=dev) if keep_chsum else None
     scale, shift, mean, invstd = _gn_tables(slab, Bs, rps // tile, Cout, rps, gamma, beta, cfg, offset, chsum)
-    arg = None
+    arg = ystar = None
     if pool_K:
         Gp = P // pool_K
         out = torch.empty(Gp, Cout, dtype=torch.float32, device=dev)
         arg = torch.empty(Gp, Cout, dtype=torch.int32, device=dev)
         if cand is not None:    # (max, argmax, min, argmin) per 32 rows from the product's epilogue: Y is not read again
+            if Y is None:       # ... and the backward gets the winners' values from here
+                ystar = torch.empty(Gp, Cout, dtype=torch.float32, device=dev)
             call("prifit_pool_from_candidates", ptr(cand), ptr(scale), ptr(shift), Gp, pool_K, Cout, rps, _F(slope), ptr(out),
                  _LL(Cout), ptr(arg), ptr(ystar), cur_stream())
         else:
@@ -208,47 +257,44 @@ def _gn_forward(Y, slab, tile, gamma, beta, cfg, offset=None, cand=None, chsum=N
         out = torch.empty(P, Cout, dtype=torch.float32, device=dev)
         call("prifit_affine_relu", ptr(Y), _LL(Cout), ptr(scale), ptr(shift), P, Cout, rps, _F(slope), ptr(out),
              _LL(Cout), cur_stream())
-    return out, scale, shift, mean, invstd, arg
+    return out, GNState(scale, shift, mean, invstd, arg, chsum, ystar)
 
 
-def _gn_backward(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, chsum=None, sums=None):
-    """Gradient of _gn_forward w.r.t. Y (written as dY [P, C]), gamma and beta.  chsum (the forward's, _gn_tables) and a dict
-    `sums`: sums["dsum"] [Bs, C] = the column sums of dY per sample, sums["db"] [C] = over all rows."""
-    gout, ca, cb, cd, dgamma, dbeta = _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, chsum, sums)
+def _gn_backward(gout, Y, gamma, state, cfg):
+    """Gradient of _gn_forward w.r.t. Y (written as dY [P, C]): (dY, GNGrads)."""
+    g = _gn_backward_coefs(gout, Y, gamma, state, cfg)
     P, Cout = Y.shape
     rps, slope, pool_K = cfg["rps"], cfg["slope"], cfg["pool_K"]
     dY = torch.empty(P, Cout, dtype=torch.float32, device=Y.device)
     if pool_K:
-        call("prifit_pool_bwd_apply", ptr(gout), _LL(gout.stride(0)), ptr(Y), _LL(Cout), ptr(arg), ptr(scale),
-             ptr(shift), ptr(ca), ptr(cb), ptr(cd), P // pool_K, pool_K, Cout, rps, _F(slope), ptr(dY), _LL(Cout),
+        call("prifit_pool_bwd_apply", ptr(g.gout), _LL(g.gout.stride(0)), ptr(Y), _LL(Cout), ptr(state.arg), ptr(state.scale),
+             ptr(state.shift), ptr(g.ca), ptr(g.cb), ptr(g.cd), P // pool_K, pool_K, Cout, rps, _F(slope), ptr(dY), _LL(Cout),
              cur_stream())
     else:
-        call("prifit_bn_relu_bwd_apply", ptr(gout), _LL(gout.stride(0)), ptr(Y), _LL(Cout), ptr(scale), ptr(shift),
-             ptr(ca), ptr(cb), ptr(cd), P, Cout, rps, _F(slope), ptr(dY), _LL(Cout), cur_stream())
-    return dY, dgamma, dbeta
+        call("prifit_bn_relu_bwd_apply", ptr(g.gout), _LL(g.gout.stride(0)), ptr(Y), _LL(Cout), ptr(state.scale), ptr(state.shift),
+             ptr(g.ca), ptr(g.cb), ptr(g.cd), P, Cout, rps, _F(slope), ptr(dY), _LL(Cout), cur_stream())
+    return dY, g
 
 
-def _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, chsum=None, sums=None):
-    """The reduction half of the GroupNorm backward: (gout contiguous, ca, cb, cd [Bs, C], dgamma, dbeta) with
-    dY = ca * act'(.) * g + cb * Y + cd.  Y None (the cloud-pooled layer whose product was not stored): sums["ystar"] holds the
-    winners' pre-activations, sums["shape"] = (P, Cout)."""
-    P, Cout = sums["shape"] if Y is None else Y.shape
+def _gn_backward_coefs(gout, Y, gamma, state, cfg):
+    """The reduction half of the GroupNorm backward: GNGrads.  Y None (the cloud-pooled layer whose product was not stored):
+    state.ystar holds the winners' pre-activations and gives the shape."""
+    scale, shift, mean, invstd, arg, chsum, ystar = state
     G, rps, slope, pool_K = cfg["groups"], cfg["rps"], cfg["slope"], cfg["pool_K"]
+    P, Cout = (ystar.shape[0] * pool_K, ystar.shape[1]) if Y is None else Y.shape
     Bs = P // rps
     dev = gout.device
     gout = gout.contiguous()
     rows = query("prifit_reduce_rows_per_slab")
+    gm = None
     if pool_K and pool_K == rps:
         # one pooling group per sample (the global max over a cloud, src/dgcnn.py:197): the per-sample partials are the
         # winners' terms themselves, [Bs, C] numbers -- (sum Gm, sum Gm * yhat) with Gm = act'(.) * gout at the winning row
         Gp = P // pool_K
-        ystar = None if sums is None else sums.get("ystar")
         yw = ystar if ystar is not None else torch.gather(Y.view(Gp, pool_K, Cout), 1, arg.long().unsqueeze(1)).squeeze(1)   # [Bs, C]
         gm = torch.where(yw * scale + shift > 0, gout, gout * slope)
         slab = torch.stack([gm, gm * ((yw - mean) * invstd)], dim=1).contiguous()                # [Bs, 2, C]
         nslab = Gp
-        if sums is not None:
-            sums["gm"] = gm
     elif pool_K:
         Gp = P // pool_K
         rows = query("prifit_pool_reduce_groups_per_slab")
@@ -263,14 +309,13 @@ def _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, chs
              ptr(mean), ptr(invstd), P, Cout, rps, _F(slope), ptr(slab), cur_stream())
     m = float(cfg.get("count_rows", rps) * (Cout // G))     # count_rows: Y is a per-group table of a tensor with more rows
     ca = scale.contiguous()
+    dsum = db = None
     if _GN_KERNELS and query("prifit_gn_finalize_supported", Cout, G):
         cb, cd = (torch.empty(Bs, Cout, dtype=torch.float32, device=dev) for _ in range(2))
         S = torch.empty(Bs, 2, Cout, dtype=torch.float64, device=dev)
-        dsum = db = None
         if chsum is not None:
             dsum = torch.empty(Bs, Cout, dtype=torch.float32, device=dev)
             db = torch.empty(Cout, dtype=torch.float32, device=dev)
-            sums["dsum"], sums["db"] = dsum, db
         call("prifit_gn_bwd_finalize", ptr(slab), Bs, nslab // Bs, Cout, G, _D(m), ptr(gamma.contiguous()), ptr(mean),
              ptr(invstd), ptr(cb), ptr(cd), ptr(S), ptr(chsum), _D(float(rps)), ptr(dsum), cur_stream())
         dgamma, dbeta = (torch.empty(Cout, dtype=torch.float32, device=dev) for _ in range(2))
@@ -287,7 +332,7 @@ def _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, chs
         isd, mu = invstd.double(), mean.double()
         cb = (-(isd * isd) * m2c).float().contiguous()
         cd = (-isd * m1c + mu * isd * isd * m2c).float().contiguous()
-    return gout, ca, cb, cd, dgamma, dbeta
+    return GNGrads(gout, ca, cb, cd, dgamma, dbeta, dsum, db, gm)
 
 
 def pool_product_ok(P, Cout, Kin):
@@ -295,9 +340,28 @@ def pool_product_ok(P, Cout, Kin):
     return Kin % 4 == 0 and bool(query("prifit_gemm_pool_supported", P, Cout, Kin))
 
 
-def _global_pool_alg_ok(P, rps, Cout, Kin, x):
-    return bool(_GLOBAL_POOL_ALG and query("prifit_global_pool_winners_supported", Cout, Kin) and rps % 512 == 0 and
-                x.data_ptr() % 16 == 0)
+ConvRoute = namedtuple("ConvRoute", "tile keep_chsum product store_y backward")
+
+
+def _conv_block_route(P, Cout, Kin, cfg, has_bias, has_offset, x):
+    """How ConvGNActFn runs x [P, Kin] -> [P, Cout]: rows per statistics slab (64 or 128), whether the column sums
+    of Y are kept, the product ("pool": the persistent kernel that leaves pool candidates, or "gemm"), whether Y is stored,
+    the backward ("alg": _global_pool_alg_bwd, or "dense").  Launches nothing; switches and queries are read at every call."""
+    rps, pool_K = cfg["rps"], cfg["pool_K"]
+    tile = query("prifit_gemm_stats_tile_m", P, Cout)
+    # a bias or an offset in front of the normalisation: their gradients are column sums of dY, which the backward's
+    # finalize gives from the statistics alone if the forward keeps the column sums of Y (24 x C numbers)
+    keep_chsum = bool((has_bias or has_offset) and _GN_COLSUMS and _GN_KERNELS and query("prifit_gn_finalize_supported", Cout, cfg["groups"]))
+    # the pooled layer on the persistent kernel: its epilogue leaves the per-32-row (max, argmax, min, argmin)
+    # candidates, so neither the pool nor an activation pass reads Y again
+    pooled = bool(pool_K and pool_K % 32 == 0 and tile == 128 and pool_product_ok(P, Cout, Kin))
+    # the layer pooled over the whole cloud: everything from the statistics, the input and B x Cout winners (their values
+    # from the candidates' pool, or gathered from a stored Y)
+    alg = bool(pool_K and pool_K == rps and keep_chsum and not has_offset and _GLOBAL_POOL_ALG and
+               query("prifit_global_pool_winners_supported", Cout, Kin) and rps % 512 == 0 and x.data_ptr() % 16 == 0)
+    # ... then nothing reads Y but the winners' values: the product is not stored (201 MB at B = 24 x 2048 x 1024)
+    store_y = not (pooled and alg and _GLOBAL_POOL_NOSTORE)
+    return ConvRoute(tile, keep_chsum, "pool" if pooled else "gemm", store_y, "alg" if alg else "dense")
 
 
 def _global_pool_alg_bwd(x, W, bias, ca, cb, cd, gm, arg, rps, need_dx, need_dW):
@@ -354,75 +418,46 @@ class ConvGNActFn(torch.autograd.Function):
         Cout = W.shape[0]
         assert cfg["rps"] % 512 == 0
         dev = x.device
-        tile = query("prifit_gemm_stats_tile_m", P, Cout)   # rows per statistics slab (divides rps: 64 or 128)
-        nslab = (P + tile - 1) // tile
-        slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
-        # a bias or an offset in front of the normalisation: their gradients are column sums of dY, which the backward's
-        # finalize gives from the statistics alone if the forward keeps the column sums of Y (24 x C numbers)
-        chsum = None
-        if (bias is not None or offset is not None) and _GN_COLSUMS and _GN_KERNELS and query("prifit_gn_finalize_supported", Cout, cfg["groups"]):
-            chsum = torch.empty(P // cfg["rps"], Cout, dtype=torch.float64, device=dev)
-        cand = ystar = None
-        pooled_tiled = bool(cfg["pool_K"] and cfg["pool_K"] % 32 == 0 and tile == 128 and pool_product_ok(P, Cout, Kin))
-        # the layer pooled over the whole cloud, backward in the algebraic form: nothing reads Y but the winners' values, which
-        # the pool leaves in `ystar` -- the product is not stored (201 MB at B = 24 x 2048 x 1024)
-        nostore = bool(pooled_tiled and _GLOBAL_POOL_NOSTORE and cfg["pool_K"] == cfg["rps"] and chsum is not None and
-                       offset is None and _global_pool_alg_ok(P, cfg["rps"], Cout, Kin, x))
-        Y = None if nostore else torch.empty(P, Cout, dtype=torch.float32, device=dev)
-        if pooled_tiled:
-            # the pooled layer on the persistent kernel: its epilogue leaves the per-32-row (max, argmax, min, argmin)
-            # candidates, so neither the pool nor an activation pass reads Y again
+        route = _conv_block_route(P, Cout, Kin, cfg, bias is not None, offset is not None, x)
+        slab = torch.empty((P + route.tile - 1) // route.tile, 2, Cout, dtype=torch.float32, device=dev)
+        Y = torch.empty(P, Cout, dtype=torch.float32, device=dev) if route.store_y else None
+        cand = None
+        if route.product == "pool":
             cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
-            if nostore:
-                ystar = torch.empty(P // cfg["pool_K"], Cout, dtype=torch.float32, device=dev)
             call("prifit_gemm_pool_f32", P, Cout, Kin, ptr(x), _LL(Kin), ptr(W), _LL(Kin), ptr(Y), _LL(Cout), None, None,
                  ptr(bias), ptr(slab), ptr(cand), cur_stream())
         else:
             gemm(NT, P, Cout, Kin, x, Kin, W, Kin, Y, Cout, bias=bias, stats=slab, tiled_stats=True)
-        out, scale, shift, mean, invstd, arg = _gn_forward(Y, slab, tile, gamma, beta, cfg, offset, cand, chsum, (P, Cout), ystar)
-        ctx.ystar = ystar
-        ctx.cfg = cfg
-        ctx.has_bias = bias is not None
-        ctx.has_offset = offset is not None
-        ctx.chsum = chsum
-        ctx.bias = bias
-        ctx.save_for_backward(x, W, gamma, Y, scale, shift, mean, invstd, *([arg] if arg is not None else []))
+        out, state = _gn_forward(Y, slab, route.tile, gamma, beta, cfg, offset, cand, route.keep_chsum, (P, Cout))
+        ctx.cfg, ctx.route, ctx.bias, ctx.has_offset = cfg, route, bias, offset is not None
+        _save_gn(ctx, state, x, W, gamma, Y)
         return out
 
     @staticmethod
     def backward(ctx, gout):
         cfg = ctx.cfg
-        x, W, gamma, Y, scale, shift, mean, invstd = ctx.saved_tensors[:8]
-        arg = ctx.saved_tensors[8] if len(ctx.saved_tensors) > 8 else None
+        (x, W, gamma, Y), state = _saved_gn(ctx, 4)
         P, Kin = x.shape
         Cout = W.shape[0]
-        dev = x.device
-        sums = {}
-        if ctx.ystar is not None:
-            sums["ystar"], sums["shape"] = ctx.ystar, (P, Cout)
-        if Y is None or (cfg["pool_K"] and cfg["pool_K"] == cfg["rps"] and ctx.chsum is not None and not ctx.has_offset and
-                         _global_pool_alg_ok(P, cfg["rps"], Cout, Kin, x)):
-            # the layer pooled over the whole cloud: everything from the statistics, the input and B x Cout winners
-            gout, ca, cb, cd, dgamma, dbeta = _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, ctx.chsum, sums)
-            dx, dW = _global_pool_alg_bwd(x, W, ctx.bias, ca, cb, cd, sums["gm"], arg, cfg["rps"], ctx.needs_input_grad[0],
-                                          ctx.needs_input_grad[1])
-            db = sums["db"] if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-            return dx, dW, db, dgamma, dbeta, None, None
-        dY, dgamma, dbeta = _gn_backward(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg, ctx.chsum, sums)
-        dW = nn_ops._weight_grad(dY, P, Cout, x, Kin, None) if ctx.needs_input_grad[1] else None
-        doff = None
-        if ctx.has_offset and ctx.needs_input_grad[6]:
+        need = ctx.needs_input_grad
+        has_bias = ctx.bias is not None
+        if ctx.route.backward == "alg":
+            g = _gn_backward_coefs(gout, Y, gamma, state, cfg)
+            dx, dW = _global_pool_alg_bwd(x, W, ctx.bias, g.ca, g.cb, g.cd, g.gm, state.arg, cfg["rps"], need[0], need[1])
+            return dx, dW, (g.db if has_bias and need[2] else None), g.dgamma, g.dbeta, None, None
+        dY, g = _gn_backward(gout, Y, gamma, state, cfg)
+        dW = nn_ops._weight_grad(dY, P, Cout, x, Kin, None) if need[1] else None
+        doff = db = None
+        if ctx.has_offset and need[6]:
             # the offset reaches every row of its sample: its gradient is the column sum of dY over the sample
-            doff = sums["dsum"] if "dsum" in sums else dY.view(P // cfg["rps"], cfg["rps"], Cout).sum(dim=1)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = sums["db"] if "db" in sums else (doff.sum(dim=0) if doff is not None else dY.sum(dim=0))
-        else:
-            db = None
+            doff = g.dsum if g.dsum is not None else dY.view(P // cfg["rps"], cfg["rps"], Cout).sum(dim=1)
+        if has_bias and need[2]:
+            db = g.db if g.db is not None else (doff.sum(dim=0) if doff is not None else dY.sum(dim=0))
         dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(P, Kin, dtype=torch.float32, device=dev)
+        if need[0]:
+            dx = torch.empty(P, Kin, dtype=torch.float32, device=x.device)
             gemm(NN, P, Kin, Cout, dY, Cout, W, Kin, dx, Kin)
-        return dx, dW, db, dgamma, dbeta, None, doff
+        return dx, dW, db, g.dgamma, g.dbeta, None, doff
 
 
 class GNActFn(torch.autograd.Function):
@@ -431,17 +466,16 @@ class GNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Y, slab, gamma, beta, cfg):
-        out, scale, shift, mean, invstd, arg = _gn_forward(Y, slab, query("prifit_reduce_rows_per_slab"), gamma, beta, cfg)
+        out, state = _gn_forward(Y, slab, query("prifit_reduce_rows_per_slab"), gamma, beta, cfg)
         ctx.cfg = cfg
-        ctx.save_for_backward(gamma, Y, scale, shift, mean, invstd, *([arg] if arg is not None else []))
+        _save_gn(ctx, state, gamma, Y)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        gamma, Y, scale, shift, mean, invstd = ctx.saved_tensors[:6]
-        arg = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
-        dY, dgamma, dbeta = _gn_backward(gout, Y, gamma, scale, shift, mean, invstd, arg, ctx.cfg)
-        return dY, None, dgamma, dbeta, None
+        (gamma, Y), state = _saved_gn(ctx, 2)
+        dY, g = _gn_backward(gout, Y, gamma, state, ctx.cfg)
+        return dY, None, g.dgamma, g.dbeta, None
 
 
 class EdgeConvLinFn(torch.autograd.Function):
@@ -463,24 +497,25 @@ class EdgeConvLinFn(torch.autograd.Function):
         # HBM: U and Vc once, the index lists, the C-wide edge pre-activations written once
         with profiler.span("edge_gather_linear", 4.0 * (2.0 * B * N * C + P + P * C)):
             call("prifit_gather_linear_fwd", ptr(U), ptr(Vc), None, ptr(idx), B, N, N, k, C, ptr(Y), ptr(slab), cur_stream())
-        out, scale, shift, mean, invstd, arg = _gn_forward(Y, slab, rows, gamma, beta, cfg)
+        out, state = _gn_forward(Y, slab, rows, gamma, beta, cfg)
         ctx.cfg, ctx.dims = cfg, (B, N, k, C)
-        ctx.save_for_backward(idx, gamma, Y, scale, shift, mean, invstd, arg)
+        _save_gn(ctx, state, idx, gamma, Y)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        idx, gamma, Y, scale, shift, mean, invstd, arg = ctx.saved_tensors
+        (idx, gamma, Y), state = _saved_gn(ctx, 3)
         B, N, k, C = ctx.dims
         cfg = ctx.cfg
-        gout, ca, cb, cd, dgamma, dbeta = _gn_backward_coefs(gout, Y, gamma, scale, shift, mean, invstd, arg, cfg)
+        g = _gn_backward_coefs(gout, Y, gamma, state, cfg)
         dU = torch.zeros(B, N, C, dtype=torch.float32, device=Y.device)
         dVc = torch.empty(B, N, C, dtype=torch.float32, device=Y.device)
         # float atomics (one per edge element into dU): priced as bytes -- Y read once, 4 B per atomic, the index lists, dVc
         with profiler.span("edge_scatter_pool", 4.0 * (2.0 * B * N * k * C + B * N * k + 2.0 * B * N * C)):
-            call("prifit_gather_linear_bwd_pool", ptr(gout), _LL(gout.stride(0)), ptr(Y), ptr(arg), ptr(scale), ptr(shift), ptr(ca),
-                 ptr(cb), ptr(cd), ptr(idx), B, N, N, k, C, cfg["rps"], _F(cfg["slope"]), ptr(dU), ptr(dVc), cur_stream())
-        return dU, dVc, None, dgamma, dbeta, None
+            call("prifit_gather_linear_bwd_pool", ptr(g.gout), _LL(g.gout.stride(0)), ptr(Y), ptr(state.arg), ptr(state.scale),
+                 ptr(state.shift), ptr(g.ca), ptr(g.cb), ptr(g.cd), ptr(idx), B, N, N, k, C, cfg["rps"], _F(cfg["slope"]), ptr(dU),
+                 ptr(dVc), cur_stream())
+        return dU, dVc, None, g.dgamma, g.dbeta, None
 
 
 class EdgeConvTabFn(torch.autograd.Function):
@@ -509,21 +544,21 @@ class EdgeConvTabFn(torch.autograd.Function):
         with profiler.span("edge_stats", 4.0 * (B * N * k + 7.0 * B * N * C)):
             call("prifit_edge_stats", ptr(U), _LL(ld), ptr(Vc), _LL(ld), int(stacked), ptr(idx), B, N, k, C, ptr(ymax), ptr(ymin),
                  ptr(karg), ptr(ysum), ptr(vct), ptr(slab), cur_stream())
-        scale, shift, mean, invstd = _gn_tables(slab, B, N // pts, C, N * k, gamma, beta, cfg)
-        call("prifit_edge_pool", ptr(ymax), ptr(ymin), ptr(scale), ptr(shift), B, N, C, _F(cfg["slope"]), ptr(out), _LL(C),
-             ptr(ystar), cur_stream())
+        state = GNState(*_gn_tables(slab, B, N // pts, C, N * k, gamma, beta, cfg), None, None, None)
+        call("prifit_edge_pool", ptr(ymax), ptr(ymin), ptr(state.scale), ptr(state.shift), B, N, C, _F(cfg["slope"]), ptr(out),
+             _LL(C), ptr(ystar), cur_stream())
         ctx.cfg, ctx.dims, ctx.stacked = cfg, (B, N, k, C), stacked
-        ctx.save_for_backward(U, vct, idx, *csr, gamma, ystar, ysum, karg, scale, shift, mean, invstd)
+        _save_gn(ctx, state, U, vct, idx, *csr, gamma, ystar, ysum, karg)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        U, vct, idx, offs, lst, pos, gamma, ystar, ysum, karg, scale, shift, mean, invstd = ctx.saved_tensors
+        (U, vct, idx, offs, lst, pos, gamma, ystar, ysum, karg), state = _saved_gn(ctx, 10)
         B, N, k, C = ctx.dims
         # the reduction half of the pooled GroupNorm backward sees only the winners: it is the unpooled reduction over the
         # [B N, C] table of winning pre-activations, with the element count of the full tensor
         cfg = dict(ctx.cfg, rps=N, pool_K=0, count_rows=N * k)
-        gout, ca, cb, cd, dgamma, dbeta = _gn_backward_coefs(gout, ystar, gamma, scale, shift, mean, invstd, None, cfg)
+        g = _gn_backward_coefs(gout, ystar, gamma, state, cfg)
         if ctx.stacked:
             dUV = torch.empty(B, N, 2 * C, dtype=torch.float32, device=U.device)
             dU, dVc, ld = dUV, dUV[:, :, C:], 2 * C
@@ -533,10 +568,10 @@ class EdgeConvTabFn(torch.autograd.Function):
         # bytes: the CSR lists and positions, U / centre terms / five tables / gout once, dU and dVc written (rows k-fold from L2)
         with profiler.span("edge_bwd_tables", 4.0 * (3.0 * B * N * k + 10.0 * B * N * C)):
             ws = torch.empty(query("prifit_edge_bwd_workspace", B, N, k, C) // 8, dtype=torch.int64, device=U.device)
-            call("prifit_edge_bwd", ptr(gout), _LL(gout.stride(0)), ptr(ystar), ptr(ysum), ptr(karg), ptr(scale), ptr(shift),
-                 ptr(ca), ptr(cb), ptr(cd), ptr(U), _LL(U.shape[2]), ptr(vct), int(ctx.stacked), ptr(idx), ptr(offs), ptr(lst),
-                 ptr(pos), B, N, k, C, _F(ctx.cfg["slope"]), ptr(dU), ptr(dVc), _LL(ld), ptr(ws), cur_stream())
-        return dU, (None if ctx.stacked else dVc), None, None, dgamma, dbeta, None
+            call("prifit_edge_bwd", ptr(g.gout), _LL(g.gout.stride(0)), ptr(ystar), ptr(ysum), ptr(karg), ptr(state.scale),
+                 ptr(state.shift), ptr(g.ca), ptr(g.cb), ptr(g.cd), ptr(U), _LL(U.shape[2]), ptr(vct), int(ctx.stacked), ptr(idx),
+                 ptr(offs), ptr(lst), ptr(pos), B, N, k, C, _F(ctx.cfg["slope"]), ptr(dU), ptr(dVc), _LL(ld), ptr(ws), cur_stream())
+        return dU, (None if ctx.stacked else dVc), None, None, g.dgamma, g.dbeta, None
 
 
 def edge_csr(idx):
@@ -550,30 +585,62 @@ def edge_csr(idx):
     return offs, lst, pos
 
 
-# The edge convolution by linearity (default): W [x_j - x_i | x_i] = Wa x_j + (Wb - Wa) x_i = U_j - Vc_i with U = X Wa^T and
-# Vc = X (Wa - Wb)^T computed once per POINT (two products over B N rows); per EDGE only a gather of Cout-wide rows of U
-# (nn_ops.GatherLinearFn, the kernel of the set-abstraction first layers).  The [B N k, 2C] edge rows of upstream
-# (src/dgcnn.py:98-105), the products over B N k rows (49 GFLOP forward at B = 24, k = 20) and their autograd (a dA and a dW
-# product over the edge rows, a 2C-wide scatter) never exist.  PRIFIT_EDGE_LINEARITY=0: rows + product (A/B arm; tested).
-_EDGE_LINEARITY = __import__("os").environ.get("PRIFIT_EDGE_LINEARITY", "1") != "0"
-# ... with its pooled GroupNorm backward formed inside the scatter (0: apply pass writes dY, then the scatter; A/B arm, tested)
-_EDGE_FUSED_BWD = __import__("os").environ.get("PRIFIT_EDGE_FUSED_BWD", "1") != "0"
-# ... and, by default, with no per-edge tensor at all (EdgeConvTabFn; 0: the pre-activations are written and re-read; A/B arm, tested)
-_EDGE_TABLES = __import__("os").environ.get("PRIFIT_EDGE_TABLES", "1") != "0"
-# the global max over the cloud fused into the mlp1 block (0: activation pass + torch max; A/B arm, tested)
-_GLOBAL_POOL_FUSED = __import__("os").environ.get("PRIFIT_GLOBAL_POOL_FUSED", "1") != "0"
-# ... and its backward in the algebraic form: no [B N, Cout] tensor dY, the two products over it replaced by per-sample
-# [Cin, Cin] products and B x Cout winners' rows (0: pool_bwd_apply + the dense dA / dW products; A/B arm, tested)
-_GLOBAL_POOL_ALG = __import__("os").environ.get("PRIFIT_GLOBAL_POOL_ALG", "1") != "0"
-# ... whose forward then does not store the product at all (0: stores it; A/B arm, tested)
-_GLOBAL_POOL_NOSTORE = __import__("os").environ.get("PRIFIT_GLOBAL_POOL_NOSTORE", "1") != "0"
+def _w2d(conv):
+    return conv.weight.reshape(conv.weight.shape[0], -1)
 
 
-def _w2d(conv, kp=None):
-    w = conv.weight.reshape(conv.weight.shape[0], -1)
-    if kp is not None and kp > w.shape[1]:
-        w = torch.cat([w, w.new_zeros(w.shape[0], kp - w.shape[1])], dim=1)
-    return w
+def _want_csr(N):
+    """Build a graph's in-edge lists (edge_csr)?  Only where _edge_route can then answer "tables"."""
+    return bool(_EDGE_TABLES and _EDGE_LINEARITY and _EDGE_FUSED_BWD and N <= 8192)
+
+
+def _edge_route(N, k, C, Cout, has_bias, csr_given):
+    """The arm of one edge convolution C -> Cout over k neighbours of N points.  Launches nothing; switches and
+    queries are read at every call.  (No arm depends on C: each pads its rows to 16 bytes.)"""
+    rows = query("prifit_reduce_rows_per_slab")
+    if not (_EDGE_LINEARITY and not has_bias and (N * k) % rows == 0 and Cout % 4 == 0):
+        return "rows"
+    # (the tables' backward reduces the [B N, Cout] table of winners in 128-row slabs: whole slabs per sample)
+    if csr_given and query("prifit_edge_tables_supported", N, k, Cout) and N % rows == 0:
+        return "tables"
+    return "linear_fused" if _EDGE_FUSED_BWD else "linear_unfused"
+
+
+def _edge_tables(X, W, C, idx, csr, gn, cfg):
+    """ONE product X [Wa; Wb]^T = [U | Vb] per point (y = U_j - U_i + Vb_i) and one [B N, 2 Cout] gradient back;
+    [Wa; Wb] is a permuted copy of the weight (one launch each way, no slices to re-assemble in the backward)."""
+    Wst = W.reshape(-1, 2, C).permute(1, 0, 2).reshape(-1, C)
+    if _pad4(C) > C:
+        X, Wst = F.pad(X, (0, _pad4(C) - C)), F.pad(Wst, (0, _pad4(C) - C))
+    UV = LinearFn.apply(X, Wst, None).view(idx.shape[0], idx.shape[1], -1)
+    return EdgeConvTabFn.apply(UV, None, idx, csr, gn.weight, gn.bias, cfg)
+
+
+def _edge_linear(X, W, C, idx, fused, gn, cfg):
+    """U and Vc per point, the edges as a gather of rows of U.  fused: EdgeConvLinFn; else the pre-activations and their
+    GroupNorm as two nodes (the backward's apply pass writes dY, then the scatter)."""
+    B, N = idx.shape[:2]
+    X, wa, wb = _pad_cols(X, _pad4(C)), _pad_cols(W[:, :C], _pad4(C)), _pad_cols(W[:, C:], _pad4(C))
+    U = LinearFn.apply(X, wa, None).view(B, N, -1)             # neighbour term, per point
+    Vc = LinearFn.apply(X, wa - wb, None).view(B, N, -1)       # minus the centre term, per point
+    if fused:
+        return EdgeConvLinFn.apply(U, Vc, idx, gn.weight, gn.bias, cfg)
+    Y, slab = nn_ops.GatherLinearFn.apply(U, Vc, None, idx, True)
+    return GNActFn.apply(Y, slab, gn.weight, gn.bias, cfg)
+
+
+def _edge_rows(feats, W, idx, gn, cfg):
+    """Upstream's form: the [B N k, 2C] edge rows, then the convolution block over them."""
+    ld = _pad4(W.shape[1])
+    return ConvGNActFn.apply(EdgeGatherFn.apply(feats, idx, ld), _pad_cols(W, ld), None, gn.weight, gn.bias, cfg)
+
+
+def _decoder_route(Cout, groups):
+    """The decoder's first layer (upstream :253-257: x4 [B,1024] repeated over the N points and concatenated with the 256 point
+    features in front of conv1, 1280 -> 512).  "offset": x4's part of that product is the same for every point of a sample --
+    ONE row per sample instead of N (4/5 of the layer's flops; the [B N, 1280] input never exists), which enters the
+    GroupNorm as a per-sample offset of the pre-activation.  "concat": upstream's rows."""
+    return "offset" if _EDGE_LINEARITY and query("prifit_gn_finalize_supported", Cout, groups) else "concat"
 
 
 class DGCNNEncoderGn(nn.Module):
@@ -598,39 +665,18 @@ class DGCNNEncoderGn(nn.Module):
         self.bnmlp1 = nn.GroupNorm(8, 1024)
 
     def _edge_conv(self, feats, idx, seq, N, csr=None):
+        """feats [B,N,C], idx [B,N,k] int32, seq = (conv, GroupNorm, ...) -> [B*N, Cout] on the arm _edge_route names."""
         conv, gn = seq[0], seq[1]
-        C = feats.shape[-1]
+        B, _, C = feats.shape
         k = idx.shape[2]
-        cfg = {"groups": gn.num_groups, "rps": N * k, "slope": 0.2, "pool_K": k, "eps": gn.eps}
-        B = feats.shape[0]
-        Cout = conv.weight.shape[0]
-        if _EDGE_LINEARITY and conv.bias is None and (N * k) % query("prifit_reduce_rows_per_slab") == 0 and Cout % 4 == 0:
-            X = feats.reshape(B * N, C)
-            pad = _pad4(C) - C                          # 16-byte rows for the product kernels (the 3 input coordinates)
-            # (the backward's reduction runs over the [B N, Cout] table of winners in 128-row slabs: whole slabs per sample)
-            if csr is not None and query("prifit_edge_tables_supported", N, k, Cout) and N % query("prifit_reduce_rows_per_slab") == 0:
-                # ONE product X [Wa; Wb]^T = [U | Vb] per point (y = U_j - U_i + Vb_i) and one [B N, 2 Cout] gradient back;
-                # [Wa; Wb] is a permuted copy of the weight (one launch each way, no slices to re-assemble in the backward)
-                Wst = conv.weight.reshape(Cout, 2, C).permute(1, 0, 2).reshape(2 * Cout, C)
-                if pad:
-                    X, Wst = F.pad(X, (0, pad)), F.pad(Wst, (0, pad))
-                UV = LinearFn.apply(X, Wst, None).view(B, N, 2 * Cout)
-                return EdgeConvTabFn.apply(UV, None, idx, csr, gn.weight, gn.bias, cfg)   # [B*N, Cout]
-            w = conv.weight.reshape(Cout, 2 * C)
-            wa, wb = w[:, :C], w[:, C:]
-            if pad:
-                X = torch.cat([X, X.new_zeros(B * N, pad)], dim=1)
-                wa = torch.cat([wa, wa.new_zeros(Cout, pad)], dim=1)
-                wb = torch.cat([wb, wb.new_zeros(Cout, pad)], dim=1)
-            U = LinearFn.apply(X, wa, None).view(B, N, Cout)             # neighbour term, per point
-            Vc = LinearFn.apply(X, wa - wb, None).view(B, N, Cout)       # minus the centre term, per point
-            if _EDGE_FUSED_BWD:
-                return EdgeConvLinFn.apply(U, Vc, idx, gn.weight, gn.bias, cfg)      # [B*N, Cout]
-            Y, slab = nn_ops.GatherLinearFn.apply(U, Vc, None, idx, True)
-            return GNActFn.apply(Y, slab, gn.weight, gn.bias, cfg)
-        ld = _pad4(2 * C)
-        rows = EdgeGatherFn.apply(feats, idx, ld)
-        return ConvGNActFn.apply(rows, _w2d(conv, ld), None, gn.weight, gn.bias, cfg)   # [B*N, Cout]
+        cfg = _gn_cfg(gn, N * k, 0.2, k)
+        route = _edge_route(N, k, C, conv.weight.shape[0], conv.bias is not None, csr is not None)
+        if route == "rows":
+            return _edge_rows(feats, _w2d(conv), idx, gn, cfg)
+        X = feats.reshape(B * N, C)                            # (each arm pads it to 16-byte rows: the 3 input coordinates)
+        if route == "tables":
+            return _edge_tables(X, _w2d(conv), C, idx, csr, gn, cfg)
+        return _edge_linear(X, _w2d(conv), C, idx, route == "linear_fused", gn, cfg)
 
     def forward_cl(self, pts):
         """pts [B,N,3 or 6] -> (x4 [B,1024], x_features [B*N,256]) channels-last.  input_channels == 6 (upstream :199-222):
@@ -639,27 +685,24 @@ class DGCNNEncoderGn(nn.Module):
         normals = self.input_channels == 6
         k, k2 = self.k, self.k * (1 if normals else self.dilation_factor)
         step = k2 // k
-        tables = _EDGE_TABLES and _EDGE_LINEARITY and _EDGE_FUSED_BWD
         with torch.no_grad():
             idx1 = (_knn_normals_cl(pts, k2) if normals else _knn_cl(pts, k2))[:, :, ::step].contiguous()
-            csr1 = edge_csr(idx1) if tables and N <= 8192 else None
+            csr1 = edge_csr(idx1) if _want_csr(N) else None
         x1 = self._edge_conv(pts, idx1, self.conv1, N, csr1)
         with torch.no_grad():
             idx2 = _knn_cl(x1.detach().view(B, N, -1), k2)[:, :, ::step].contiguous()
-            csr2 = edge_csr(idx2) if tables and N <= 8192 else None
+            csr2 = edge_csr(idx2) if _want_csr(N) else None
         x2 = self._edge_conv(x1.view(B, N, -1), idx2, self.conv2, N, csr2)
         x3 = self._edge_conv(x2.view(B, N, -1), idx2, self.conv3, N, csr2)      # re-uses the second graph (:191)
         feats = torch.cat((x1, x2, x3), dim=1)
-        cfg = {"groups": self.bnmlp1.num_groups, "rps": N, "slope": 0.0, "pool_K": 0, "eps": self.bnmlp1.eps}
-        if _GLOBAL_POOL_FUSED and N % 32 == 0 and pool_product_ok(B * N, self.mlp1.weight.shape[0], feats.shape[1]):
-            # relu(gn(mlp1(.))) and the max over the cloud (upstream :194-197) as ONE pooled block with K = N: the [B N, 1024]
-            # activation is neither written nor reduced by a separate pass, and the backward routes the gradient through the
-            # winners' indices instead of a dense [B, N, 1024] tensor of mostly zeros
-            cfg["pool_K"] = N
-            x4 = ConvGNActFn.apply(feats, _w2d(self.mlp1), self.mlp1.bias, self.bnmlp1.weight, self.bnmlp1.bias, cfg)
-            return x4, feats
-        h = ConvGNActFn.apply(feats, _w2d(self.mlp1), self.mlp1.bias, self.bnmlp1.weight, self.bnmlp1.bias, cfg)
-        x4 = h.view(B, N, -1).max(dim=1)[0]
+        # relu(gn(mlp1(.))) and the max over the cloud (upstream :194-197) as ONE pooled block with K = N: the [B N, 1024]
+        # activation is neither written nor reduced by a separate pass, and the backward routes the gradient through the
+        # winners' indices instead of a dense [B, N, 1024] tensor of mostly zeros
+        pool_K = N if _GLOBAL_POOL_FUSED and N % 32 == 0 and pool_product_ok(B * N, self.mlp1.weight.shape[0], feats.shape[1]) else 0
+        x4 = ConvGNActFn.apply(feats, _w2d(self.mlp1), self.mlp1.bias, self.bnmlp1.weight, self.bnmlp1.bias,
+                               _gn_cfg(self.bnmlp1, N, 0.0, pool_K))
+        if not pool_K:
+            x4 = x4.view(B, N, -1).max(dim=1)[0]
         return x4, feats
 
     def forward(self, x):
@@ -685,22 +728,16 @@ class DGCNGn(nn.Module):
         self.mlp_segmentation = nn.Conv1d(256, 3, 1)
 
     def _block(self, x, conv, gn, N):
-        cfg = {"groups": gn.num_groups, "rps": N, "slope": 0.0, "pool_K": 0, "eps": gn.eps}
-        return ConvGNActFn.apply(x, _w2d(conv), conv.bias, gn.weight, gn.bias, cfg)
+        return ConvGNActFn.apply(x, _w2d(conv), conv.bias, gn.weight, gn.bias, _gn_cfg(gn, N, 0.0))
 
     def forward(self, points):
         B, _, N = points.shape
         x4, feats = self.encoder.forward_cl(points.transpose(1, 2).contiguous())
-        if _EDGE_LINEARITY and query("prifit_gn_finalize_supported", self.conv1.weight.shape[0], self.bn1.num_groups):
-            # upstream :253-257 repeats the global feature x4 [B,1024] over the N points and concatenates it with the 256
-            # point features in front of conv1 (1280 -> 512).  The x4 part of that product is the same for every point of a
-            # sample: ONE row per sample (24 x 1024 x 512) instead of N (49152 x 1024 x 512, 4/5 of the layer's flops, and the
-            # [B N, 1280] input never exists); it enters the GroupNorm as a per-sample offset of the pre-activation.
-            w = self.conv1.weight.reshape(self.conv1.weight.shape[0], -1)
+        if _decoder_route(self.conv1.weight.shape[0], self.bn1.num_groups) == "offset":
+            w = _w2d(self.conv1)
             w4, wf = w[:, :1024].contiguous(), w[:, 1024:].contiguous()
             off = LinearFn.apply(x4.contiguous(), w4, self.conv1.bias)                      # [B, 512], bias included
-            cfg = {"groups": self.bn1.num_groups, "rps": N, "slope": 0.0, "pool_K": 0, "eps": self.bn1.eps}
-            x = ConvGNActFn.apply(feats, wf, None, self.bn1.weight, self.bn1.bias, cfg, off)
+            x = ConvGNActFn.apply(feats, wf, None, self.bn1.weight, self.bn1.bias, _gn_cfg(self.bn1, N, 0.0), off)
         else:
             x = torch.cat([x4.unsqueeze(1).expand(B, N, 1024).reshape(B * N, 1024), feats], dim=1)
             x = self._block(x, self.conv1, self.bn1, N)
@@ -724,7 +761,6 @@ class get_model(nn.Module):
     def forward(self, xyz, cls_label=None, chamfer_points=0, include_convex_loss=False, quantile=0.01,
                 msc_iterations=5, max_num_clusters=25, fit_inputs=None, **_unused):
         if xyz.is_cuda:
-            from .. import arena as zero_pool
             zero_pool.begin_step(xyz.device)
         emb, seg = self.net(xyz)
         xyz = xyz[:, :3]                     # the loss sees positions only (normal_channel=True: rows 3..5 are normals)
