@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 200
+#define PRIFIT_ABI_VERSION 300
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -868,6 +868,26 @@ int prifit_cuboid_sample_nn_bwd(const float *r, const float *V, const float *c, 
                                 const int32_t *off, int B, int KM, const float *targets, int M, int cap,
                                 const int32_t *nn_idx, const float *gscale, float *g_r, float *g_V,
                                 float *g_c, void *stream);
+
+/* Point-set Chamfer distance: the exact nearest neighbour between two batched, ragged clouds and its gradient to both.
+ * Replaces the [N, M] pairwise matrix + torch.min of src/utils.py:271-294 (chamfer_distance), :297-321
+ * (chamfer_distance_one_side) and :324-358 (chamfer_distance_single_shape), and the host KD-tree query + gather of :361-381
+ * (chamfer_distance_kdtree) and :413-416 (the source half of analytic_chamfer_distance).
+ * a [B,NA,3] queries, b [B,NB,3] targets; na / nb [B] device counts of live rows per shape (NULL = all): rows at or past
+ * the count are never read.  fp32 in one fixed order, no fma, so that a numpy restatement gives the same bits:
+ *   d2 [B,NA]  = min_j ((dx*dx + dy*dy) + dz*dz), dx = a.x - b.x ... (direct differences, not the expanded form)
+ *   idx [B,NA] = the lowest j attaining it; rows past na[s], and every row of a shape with nb[s] == 0: d2 = 0, idx = -1.
+ * workspace: prifit_chamfer_nn_workspace_floats(B, NA, NB) floats (8-byte aligned; may be NULL when that is 0): below ~4
+ * workgroups per CU the targets are searched in several ranges in parallel and a second launch keeps the first minimum.
+ * _bwd: g [B,NA] = d L / d d2 -> ga [B,NA,3] = (2 g) * (a - b[idx]) per component (dead rows 0; always written, it is also
+ * the backward's scratch), gb [B,NB,3] = ((0 - ga[i0]) - ga[i1]) - ... over the rows i with idx[s,i] == j in ascending i
+ * (unreferenced and dead rows 0); accumulate_b != 0 adds that onto what gb holds (the two-sided distance, where b is a
+ * query set as well).  No floating-point atomics: the same bits from run to run. */
+long long prifit_chamfer_nn_workspace_floats(int B, int NA, int NB);
+int prifit_chamfer_nn_fwd(const float *a, const float *b, const int32_t *na, const int32_t *nb, int B, int NA, int NB,
+                          float *d2, int32_t *idx, float *workspace, void *stream);
+int prifit_chamfer_nn_bwd(const float *a, const float *b, const int32_t *na, const int32_t *nb, int B, int NA, int NB,
+                          const int32_t *idx, const float *g, float *ga, float *gb, int accumulate_b, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* DGCNN graph ops (src/dgcnn.py, BASELINE.json configs[4])                                     */

@@ -34,6 +34,7 @@ SOURCES = {
     "meanshift_split.hip": [],
     "fit.hip": [],
     "fit_glue.hip": [],
+    "chamfer.hip": ["-ffp-contract=off"],
     "optim.hip": [],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],

@@ -16,7 +16,7 @@ import torch
 
 from . import profiler
 from . import arena as zero_pool
-from ._lib import call, cur_stream, dll, ptr, query
+from ._lib import call, cur_stream, dll, ptr, query, require_cuda
 from .nn_ops import EPI_CHORD, EPI_MSBWD, EPI_MSKERNEL, NN, NT, TN, gemm
 
 _LL = ctypes.c_longlong
@@ -601,6 +601,53 @@ class SampleNNLossFn(torch.autograd.Function):
             call(ctx.pre + "_nn_bwd", ptr(r), ptr(V), ptr(c), ptr(n), ptr(off), Bt, K, ptr(targets), M, ctx.cap,
                  ptr(nn_idx), ptr(gs.contiguous()), ptr(g_r), ptr(g_V), ptr(g_c), cur_stream())
         return g_r, g_V, g_c, None, None, None
+
+
+class ChamferNNFn(torch.autograd.Function):
+    """Exact nearest neighbour between two batched point sets: a [B,NA,3] queries, b [B,NB,3] targets, na / nb [B] int32
+    counts of live rows (None = all) -> (d2 [B,NA] squared distance to the nearest live target, idx [B,NA] int32 its index,
+    the lowest on ties; -1 and d2 = 0 on dead rows).  What the [N,M] matrix + min of src/utils.py:284-292, :311-319, :338-353
+    and the KD-tree query + gather of :368-374, :413-416 compute, without the matrix.  Gradients flow to a and b."""
+
+    @staticmethod
+    def forward(ctx, a, b, na=None, nb=None):
+        require_cuda(a, b, na, nb)
+        a, b = a.contiguous(), b.contiguous()
+        if a.dtype != torch.float32 or b.dtype != torch.float32:
+            raise TypeError("ChamferNNFn: float32 point sets expected, got %s / %s" % (a.dtype, b.dtype))
+        if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or a.shape[0] != b.shape[0]:
+            raise ValueError("ChamferNNFn: a [B,NA,3] and b [B,NB,3] expected, got %s / %s" % (tuple(a.shape), tuple(b.shape)))
+        Bt, NA, NB = a.shape[0], a.shape[1], b.shape[1]
+        dev = a.device
+        na = None if na is None else na.to(torch.int32).contiguous()
+        nb = None if nb is None else nb.to(torch.int32).contiguous()
+        d2 = torch.empty(Bt, NA, dtype=torch.float32, device=dev)
+        idx = torch.empty(Bt, NA, dtype=torch.int32, device=dev)
+        nws = query("prifit_chamfer_nn_workspace_floats", Bt, NA, NB)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
+        # VALU-bound exact search, 11 operations per pair (3 sub, 3 mul, 2 add, compare + 2 selects)
+        with profiler.span("chamfer_nn", 11.0 * Bt * NA * NB):
+            call("prifit_chamfer_nn_fwd", ptr(a), ptr(b), ptr(na), ptr(nb), Bt, NA, NB, ptr(d2), ptr(idx), ptr(ws),
+                 cur_stream())
+        ctx.save_for_backward(a, b, idx, *[t for t in (na, nb) if t is not None])
+        ctx.has = (na is not None, nb is not None)
+        ctx.mark_non_differentiable(idx)
+        return d2, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gidx):
+        a, b, idx = ctx.saved_tensors[:3]
+        rest = list(ctx.saved_tensors[3:])
+        na = rest.pop(0) if ctx.has[0] else None
+        nb = rest.pop(0) if ctx.has[1] else None
+        Bt, NA, NB = a.shape[0], a.shape[1], b.shape[1]
+        ga, gb = torch.empty_like(a), torch.empty_like(b)
+        # HBM: per query its index, gradient, row and gathered target in, its row out; the target side re-reads idx + ga per wave
+        with profiler.span("chamfer_nn_bwd", Bt * (NA * (4.0 + 4.0 + 12.0 + 12.0 + 12.0) + NB * 12.0)):
+            call("prifit_chamfer_nn_bwd", ptr(a), ptr(b), ptr(na), ptr(nb), Bt, NA, NB, ptr(idx), ptr(g.contiguous()), ptr(ga),
+                 ptr(gb), 0, cur_stream())
+        return ga, gb, None, None
 
 
 class ChamferCombineFn(torch.autograd.Function):

@@ -62,7 +62,15 @@ class Loss:
     ground-truth cloud and the resampled surface points."""
 
     def loss(self, gt_points, sampled_points):
-        from .utils import chamfer_distance_kdtree
-        d = [chamfer_distance_kdtree(sampled_points[b].unsqueeze(0), gt_points[b].unsqueeze(0))
-             for b in range(gt_points.shape[0]) if torch.is_tensor(sampled_points[b])]
-        return torch.mean(torch.stack(d))
+        """gt_points [B,N,3]; sampled_points: per shape an [n_b,3] tensor (or a non-tensor for a shape without samples, which
+        is left out).  Per shape (mean_t |t - NN_sampled(t)|^2 + mean_s |s - NN_gt(s)|^2) / 2 as chamfer_distance_kdtree; the
+        ragged sample lists are packed with counts: one search per direction for the whole batch."""
+        from .utils import nn_d2, pack_clouds
+        live = [b for b in range(gt_points.shape[0]) if torch.is_tensor(sampled_points[b])]
+        if not live:
+            raise RuntimeError("Loss.loss: no shape has sampled points")
+        src, ns, nsf = pack_clouds([sampled_points[b] for b in live])
+        gt = gt_points[torch.tensor(live, device=gt_points.device)]
+        d_st = nn_d2(gt, src, nb=ns).mean(1)
+        d_ts = nn_d2(src, gt, na=ns).sum(1) / nsf                                # ragged mean: dead rows hold 0
+        return torch.mean((d_st + d_ts) / 2.0)

@@ -1,13 +1,17 @@
-"""Call surface of the loss-side helpers of the reference's src/utils.py: chamfer_distance_kdtree (:361-381) and
-analytic_chamfer_distance (:384-426).  The host KD-tree of upstream is replaced by an exact nearest-neighbour search
-on the device (any exact search agrees up to ties); the SDF half runs in the HIP kernels of csrc/fit.hip.
+"""Call surface of the loss-side helpers of the reference's src/utils.py: the point-set Chamfer distances chamfer_distance
+(:271-294), chamfer_distance_one_side (:297-321), chamfer_distance_single_shape (:324-358), chamfer_distance_kdtree (:361-381)
+and analytic_chamfer_distance (:384-426).  Upstream's [N,M] distance matrix and its host KD-tree are both replaced by one exact
+nearest-neighbour search on the device, batched over shapes and differentiable (fit_ops.ChamferNNFn, csrc/chamfer.hip; any
+exact search agrees up to ties, and ties go to the lowest index); the SDF half runs in the HIP kernels of csrc/fit.hip.
 
 The fused form of analytic_chamfer_distance used by the training step (sampling + search in one kernel, fixed-capacity
 parameter tensors) is prifit_amd.convex_loss.analytic_chamfer_distance; this module keeps upstream's list-based
 signature for stand-alone callers (fitting.py)."""
+import numpy as np
 import torch
 
 from .. import fit_ops
+from .guard import guard_sqrt
 
 
 def nearest_index(src, tgt, chunk=4096):
@@ -20,18 +24,76 @@ def nearest_index(src, tgt, chunk=4096):
     return torch.cat(out)
 
 
+def _points(x):
+    """upstream :278-282: numpy clouds go to the device as float32; tensors are taken as they are (device tensors only)."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x.astype(np.float32)).cuda()
+    return x if x.dtype == torch.float32 else x.float()
+
+
+def nn_d2(a, b, na=None, nb=None):
+    """[B,NA] squared distance from every row of a [B,NA,3] to its nearest row of b [B,NB,3] (na / nb: live rows per shape;
+    dead rows give 0), differentiable in both."""
+    return fit_ops.ChamferNNFn.apply(a, b, na, nb)[0]
+
+
+def pack_clouds(clouds):
+    """list of [n_i,3] device tensors -> ([len, max n_i, 3] zero-padded, [len] int32 counts on the device, [len] float counts)."""
+    pts = torch.nn.utils.rnn.pad_sequence([_points(c) for c in clouds], batch_first=True)
+    cnt = torch.tensor([c.shape[0] for c in clouds], dtype=torch.int32, device=pts.device)
+    return pts, cnt, cnt.to(torch.float32)
+
+
+def chamfer_distance(pred, gt, sqrt=False):
+    """upstream :271-294: pred [B,N,3], gt [B,M,3] -> mean over shapes of (mean_n min_m d + mean_m min_n d) / 2 with d the
+    squared distance, or guard_sqrt of it (clamp at 1e-5, then sqrt: monotone, so it is applied to the minima)."""
+    pred, gt = _points(pred), _points(gt)
+    d_pg, d_gp = nn_d2(pred, gt), nn_d2(gt, pred)
+    if sqrt:
+        d_pg, d_gp = guard_sqrt(d_pg), guard_sqrt(d_gp)
+    return torch.mean(d_pg.mean(1) + d_gp.mean(1)) / 2.0
+
+
+def chamfer_distance_one_side(pred, gt, side=1):
+    """upstream :297-321: side 0 = every pred point to its nearest gt point (mean over N), side 1 = every gt point to its
+    nearest pred point (mean over M); then the mean over shapes.  Upstream leaves any other `side` undefined."""
+    pred, gt = _points(pred), _points(gt)
+    if side == 0:
+        d = nn_d2(pred, gt)
+    elif side == 1:
+        d = nn_d2(gt, pred)
+    else:
+        raise ValueError("chamfer_distance_one_side: side must be 0 or 1, got %r" % (side,))
+    return torch.mean(d.mean(1))
+
+
+def chamfer_distance_single_shape(pred, gt, one_side=False, sqrt=False, reduce=True):
+    """upstream :324-358: pred [N,3], gt [M,3].  one_side: every gt point to its nearest pred point ([M], or its mean);
+    otherwise (pred -> gt [N] + gt -> pred [M]) / 2, of the means when `reduce`, else of the vectors themselves, which
+    needs N == M as upstream's broadcast does."""
+    pred, gt = _points(pred), _points(gt)
+    if not one_side and not reduce and pred.shape[0] != gt.shape[0]:
+        raise ValueError("chamfer_distance_single_shape(reduce=False): two-sided form adds an [N] and an [M] vector, "
+                         "N = %d, M = %d" % (pred.shape[0], gt.shape[0]))
+    p, g = pred.unsqueeze(0), gt.unsqueeze(0)
+    fin = guard_sqrt if sqrt else (lambda d: d)
+    cd2 = fin(nn_d2(g, p)[0])
+    if one_side:
+        return torch.mean(cd2, 0) if reduce else cd2
+    cd1 = fin(nn_d2(p, g)[0])
+    if reduce:
+        cd1, cd2 = torch.mean(cd1), torch.mean(cd2)
+    return (cd1 + cd2) / 2.0
+
+
 def chamfer_distance_kdtree(source_points, target_points, sqrt=False):
     """upstream :361-381: source_points [B,S,3], target_points [B,T,3] -> mean over shapes of
-    (mean_t |t - NN_source(t)|^2 + mean_s |s - NN_target(s)|^2) / 2."""
-    per = []
-    for b in range(source_points.shape[0]):
-        s, t = source_points[b], target_points[b]
-        d_st = ((t - s[nearest_index(t, s)]) ** 2).sum(1)
-        d_ts = ((s - t[nearest_index(s, t)]) ** 2).sum(1)
-        if sqrt:
-            d_st, d_ts = torch.sqrt(d_st), torch.sqrt(d_ts)
-        per.append((d_st.mean() + d_ts.mean()) / 2.0)
-    return torch.stack(per).mean()
+    (mean_t |t - NN_source(t)|^2 + mean_s |s - NN_target(s)|^2) / 2.  One search per direction for the whole batch."""
+    s, t = _points(source_points), _points(target_points)
+    d_st, d_ts = nn_d2(t, s), nn_d2(s, t)
+    if sqrt:
+        d_st, d_ts = torch.sqrt(d_st), torch.sqrt(d_ts)
+    return ((d_st.mean(1) + d_ts.mean(1)) / 2.0).mean()
 
 
 def pack_params(ellipsoid_params_batch, device):
@@ -60,16 +122,13 @@ def analytic_chamfer_distance(ellipsoid_params_batch, source_points, target_poin
     r, V, c, valid = pack_params(ellipsoid_params_batch, dev)
     M = target_points.shape[1]
     sdf_ts = fit_ops.SdfLossFn.apply(target_points.contiguous(), r, V, c, valid, cuboid) / M     # [B]
-    per = []
-    for b in range(target_points.shape[0]):
-        s = source_points[b]
-        if not torch.is_tensor(s):
-            continue
-        d_st = ((s - target_points[b][nearest_index(s, target_points[b])]) ** 2).sum(1)
-        per.append((d_st.mean() + sdf_ts[b]) / 2.0)
-    if not per:
+    live = [b for b in range(target_points.shape[0]) if torch.is_tensor(source_points[b])]
+    if not live:
         return torch.zeros(1, requires_grad=True, device=dev)
-    return torch.stack(per).mean()
+    src, ns, nsf = pack_clouds([source_points[b] for b in live])
+    sel = torch.tensor(live, device=dev)
+    d_st = nn_d2(src, _points(target_points)[sel], na=ns).sum(1) / nsf          # ragged mean: dead rows hold 0
+    return ((d_st + sdf_ts[sel]) / 2.0).mean()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
