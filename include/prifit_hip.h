@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 300
+#define PRIFIT_ABI_VERSION 400
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -888,6 +888,30 @@ int prifit_chamfer_nn_fwd(const float *a, const float *b, const int32_t *na, con
                           float *d2, int32_t *idx, float *workspace, void *stream);
 int prifit_chamfer_nn_bwd(const float *a, const float *b, const int32_t *na, const int32_t *nb, int B, int NA, int NB,
                           const int32_t *idx, const float *g, float *ga, float *gb, int accumulate_b, void *stream);
+
+/* Chart-batched AtlasNet decoder (models/reconstruction.py:8-70): for every chart c of num_charts and every row (b, p) of the
+ * B * P positions, conv1(130->130) bn1 relu, conv2(130->65) bn2 relu, conv3(65->32) bn3 relu, conv4(32->3) tanh on the input
+ * [grid_p (2) | z_b (128)], in 5 launches forward and 5 backward whatever num_charts and B are.  The [B,130,P] input is never
+ * formed (the z part of conv1 is one vector per shape) and the first activation is recomputed where it is consumed.
+ * params: DEVICE table [num_charts][24] of pointers, per chart: conv1.weight [130,130], conv1.bias, conv2.weight [65,130],
+ *   conv2.bias, conv3.weight [32,65], conv3.bias, conv4.weight [3,32], conv4.bias, then for bn1, bn2, bn3 each weight, bias,
+ *   running_mean, running_var, then the three num_batches_tracked (int64), one unused slot.
+ * z [B,128]; grid [2,P] (u row, v row); out [B, num_charts * P, 3], chart-major within a shape.
+ * training != 0: batch statistics over the B * P rows of a chart (biased variance), running statistics moved with `momentum`
+ *   (unbiased variance) and num_batches_tracked incremented, in place; B * P >= 2.  training == 0: the running statistics.
+ * workspace: prifit_atlas_workspace_floats(num_charts, B, P, 0) floats for _fwd, which the backward reads again
+ *   (fwd_workspace); (.., 1) floats of scratch for _bwd.  Every word that is read has been written by the same call chain.
+ * _bwd: gout [B, num_charts * P, 3] -> gz [B,128] and gparams [num_charts][28210]: per chart the gradients of conv1.weight,
+ *   conv1.bias, .. conv4.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias, bn3.weight, bn3.bias, back to back.  In training
+ *   mode the biases of conv1 .. conv3 (in front of a batch-statistics BatchNorm) get exactly 0.
+ * BatchNorm sums are per-tile partials merged in a fixed order, weight gradients per-group partials summed in a fixed order:
+ * no floating-point atomics, the same bits from run to run. */
+long long prifit_atlas_workspace_floats(int num_charts, int B, int P, int backward);
+int prifit_atlas_fwd(const void *const *params, const float *z, const float *grid, int num_charts, int B, int P, int training,
+                     float eps, float momentum, float *out, float *workspace, void *stream);
+int prifit_atlas_bwd(const void *const *params, const float *z, const float *grid, int num_charts, int B, int P, int training,
+                     const float *gout, const float *out, const float *fwd_workspace, float *workspace, float *gz,
+                     float *gparams, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 /* DGCNN graph ops (src/dgcnn.py, BASELINE.json configs[4])                                     */

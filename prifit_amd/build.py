@@ -35,6 +35,7 @@ SOURCES = {
     "fit.hip": [],
     "fit_glue.hip": [],
     "chamfer.hip": ["-ffp-contract=off"],
+    "atlas.hip": [],
     "optim.hip": [],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],

@@ -4,7 +4,7 @@
     MODEL = importlib.import_module("models.pointnet2_part_seg_msg")   # train_partseg_shapenet.py:219
 
 After `install()` the names the reference's trainer / loss import -- `models.pointnet_util`,
-`models.pointnet2_part_seg_msg`, `models.pretrain_pointnet2_part_seg_msg`, `convex_loss`,
+`models.pointnet2_part_seg_msg`, `models.pretrain_pointnet2_part_seg_msg`, `models.reconstruction`, `convex_loss`,
 `src.mean_shift`, `src.ellipsoid_fitting`, `src.ellipsoid_utils`, `src.fitting_utils`, `src.sample_ellipsoid`, `src.utils`,
 `src.guard`, `src.VisUtils`, `data_utils.ShapeNetDataLoader`, `provider`, `testing` -- are this package's modules, and every
 name `train_partseg_shapenet.py:5-28`, `testing.py:1-30` and `fitting.py:1-18` import from them resolves with the
@@ -20,6 +20,7 @@ _ALIASES = {
     "models.pointnet_utils": "prifit_amd.models.pointnet_util",
     "models.pointnet2_part_seg_msg": "prifit_amd.models.pointnet2_part_seg_msg",
     "models.pretrain_pointnet2_part_seg_msg": "prifit_amd.models.pretrain_pointnet2_part_seg_msg",
+    "models.reconstruction": "prifit_amd.models.reconstruction",
     "models.pointnet2_part_seg_ssg": "prifit_amd.models.pointnet2_part_seg_ssg",
     "models.pointnet2_cls_msg": "prifit_amd.models.pointnet2_cls_msg",
     "models.pointnet2_cls_ssg": "prifit_amd.models.pointnet2_cls_ssg",

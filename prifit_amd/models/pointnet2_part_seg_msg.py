@@ -9,7 +9,9 @@ Return contract (fixes the upstream arity bug): always the trainer
     (seg_logprob [B,N,num_parts], (l1_points, l2_points, l3_points), feat [B,128,N],
      total_loss [1,1] or [1], chamfer_loss [1,1] or [1])
 (train_partseg_shapenet.py:387,444); when include_convex_loss=True the tuple is extended by
-(labels, ellipse_params_batch, feat_embed) as in upstream :134.
+(labels, ellipse_params_batch, feat_embed) as in upstream :134.  With reconstruct=True it is upstream's 6-tuple instead
+(:131-132): the five above, total_loss including the reconstruction term and chamfer_loss zeros(1), plus
+output_points [B, num_charts * P, 3] of the AtlasNet decoder (models/reconstruction.py).
 """
 import torch
 import torch.nn as nn
@@ -25,8 +27,8 @@ class get_model(nn.Module):
     def __init__(self, num_parts, normal_channel=False, l2_norm=False, reconstruct=False, extra_layers=False,
                  num_charts=25, num_points=128):
         super().__init__()
-        if reconstruct or extra_layers:
-            raise NotImplementedError("reconstruct / extra_layers are outside the accelerated hot path")
+        if extra_layers:
+            raise NotImplementedError("extra_layers is outside the accelerated hot path")
         additional_channel = 3 if normal_channel else 0
         self.normal_channel = normal_channel
         self.l2_norm = l2_norm
@@ -48,10 +50,19 @@ class get_model(nn.Module):
         self.drop1 = nn.Dropout(0.5)
         self.conv2 = nn.Conv1d(128, num_parts, 1)
         self.extra_conv_emb = nn.Conv1d(128, 128, 1)
+        if reconstruct:                                   # upstream :60-62
+            from .reconstruction import AtlasNet, ChamferDistance
+            self.atlasnet = AtlasNet(num_charts=num_charts, num_points=num_points)
+            self.chamferdistance = ChamferDistance()
 
     def embed_features(self, xyz, cls_label, fps_start=None):
         """Backbone up to `feat` (upstream :64-88), channels-last internally.
         Returns (l1 [B,512,320], l2 [B,128,256], l3 [B,1,1024], feat [B*N,128]) channels-last."""
+        return self._embed_with_l0(xyz, cls_label, fps_start)[:4]
+
+    def _embed_with_l0(self, xyz, cls_label, fps_start=None):
+        """embed_features plus l0_up [B,N,128], the output of fp1 (upstream's l0_points, :86): the decoder's latent is its mean
+        over the points (:116), not the mean of feat."""
         with batched_bn_counters():
             return self._embed_features(xyz, cls_label, fps_start)
 
@@ -83,7 +94,7 @@ class get_model(nn.Module):
         w1 = self.conv1.weight.reshape(128, 128)
         feat = SharedMLPFn.apply(l0_up.reshape(B * N, -1), _mlp_cfg([self.bn1], 0, self.training),
                                  *_mlp_tensors([self.conv1], [self.bn1], w1))
-        return l1_up, l2_up, l3_points, feat
+        return l1_up, l2_up, l3_points, feat, l0_up.reshape(B, N, -1)
 
     def forward(self, xyz, cls_label, chamfer_points=0, include_convex_loss=False, if_cuboid=False,
                 include_intersect_loss=False, include_entropy_loss=False, include_pruning=False, quantile=0.01,
@@ -92,7 +103,10 @@ class get_model(nn.Module):
         B, C, N = xyz.shape
         if xyz.is_cuda:
             zero_pool.begin_step(xyz.device)   # one zero-fill per step for all zero-initialised fp32 buffers
-        l1, l2, l3, feat = self.embed_features(xyz, cls_label, fps_start)
+        if self.reconstruct:                               # (a captured backbone, train_step.graph_backbone, has no l0_up output)
+            l1, l2, l3, feat, l0_up = self._embed_with_l0(xyz, cls_label, fps_start)
+        else:
+            l1, l2, l3, feat = self.embed_features(xyz, cls_label, fps_start)
         if getattr(self, "after_backbone", None) is not None:
             # data-path hook (like a DataLoader worker): e.g. `net.after_backbone = lambda: net.sample_ahead(next_xyz)` starts
             # the NEXT batch's farthest-point sampling here, so that its 640 serial rounds on 24 CUs run beside the
@@ -126,12 +140,20 @@ class get_model(nn.Module):
             extra = (None, None, feat_embed.reshape(B, N, 128).permute(0, 2, 1))
         if total_loss is None:
             total_loss, chamfer_loss = torch.zeros(1, device=xyz.device), torch.zeros(1, device=xyz.device)
+        output_points = None
+        if self.reconstruct:                               # upstream :112-120
+            z = l0_up.mean(dim=1)
+            output_points = self.atlasnet(z)
+            total_loss = total_loss + self.chamferdistance(output_points, xyz.permute(0, 2, 1)[:, :, :3])
+            chamfer_loss = torch.zeros(1, device=xyz.device)
         x = self.drop1(feat)
         logits = LinearFn.apply(x, self.conv2.weight.reshape(self.conv2.weight.shape[0], 128), self.conv2.bias)
         seg = F.log_softmax(logits, dim=1).reshape(B, N, -1)
         feat_cf = feat.reshape(B, N, 128).permute(0, 2, 1)
         outs = (seg, (l1.permute(0, 2, 1), l2.permute(0, 2, 1), l3.permute(0, 2, 1)), feat_cf, total_loss,
                 chamfer_loss)
+        if self.reconstruct:                               # upstream :131-132: the 6-tuple, with the convex loss as well
+            return outs + (output_points,)
         return outs + extra
 
 
