@@ -426,6 +426,28 @@ __device__ __forceinline__ void prim_grad(int kind, const EllParam &e, const flo
     }
 }
 
+// Adds the 15 numbers v[] of every lane (g_r, g_V row-major, g_c) into s_acc[k * 15 + ..] of the lane's slot k (k < 0: nothing).
+// The lanes of one slot are summed across the wave first -- a butterfly, the same order in every run -- and one lane adds the
+// wave's total with one LDS atomic per number: a slot's sum is a tree over its lanes and a handful of wave totals instead of up
+// to 256 float atomics in arrival order (whose rounding grew with the sample count and changed from run to run).
+// Every lane of the wave must call it.
+__device__ __forceinline__ void slot_accumulate(float *s_acc, int k, const float (&v)[15])
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(k >= 0);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int kc = __shfl(k, lead, 64);
+        const bool mine = k == kc;
+#pragma unroll
+        for (int j = 0; j < 15; ++j) {
+            const float t = wave_sum_f32(mine ? v[j] : 0.f);
+            if (lane == lead) atomicAdd(s_acc + kc * 15 + j, t);
+        }
+        todo &= ~__ballot(mine);
+    }
+}
+
 constexpr int KM_MAX = 64;
 
 __global__ __launch_bounds__(256) void sdf_fwd_kernel(int kind, const float *__restrict__ tgt, int M,
@@ -488,32 +510,32 @@ __global__ __launch_bounds__(256) void sdf_bwd_kernel(int kind, const float *__r
     for (int i = threadIdx.x; i < KM * 15; i += 256) s_acc[i] = 0.f;
     __syncthreads();
     const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m < M) {
-        const int k = arg[(size_t)b * M + m];
-        if (k >= 0) {
-            const EllParam &e = s_e[k];
-            const float *p = tgt + ((size_t)b * M + m) * 3;
-            float q[3], k0, k1;
-            const float f = prim_eval(kind, e, p[0], p[1], p[2], q, k0, k1);
-            const float gf = gscale[b] * 2.0f * f;
-            float gq[3], gr[3];
-            float *acc = s_acc + k * 15;
-            prim_grad(kind, e, q, k0, k1, gf, gq, gr);
+    const int k = m < M ? arg[(size_t)b * M + m] : -1;
+    float v[15];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) atomicAdd(acc + a, gr[a]);
-            const float d[3] = {p[0] - e.c[0], p[1] - e.c[1], p[2] - e.c[2]};
+    for (int j = 0; j < 15; ++j) v[j] = 0.f;
+    if (k >= 0) {
+        const EllParam &e = s_e[k];
+        const float *p = tgt + ((size_t)b * M + m) * 3;
+        float q[3], k0, k1;
+        const float f = prim_eval(kind, e, p[0], p[1], p[2], q, k0, k1);
+        const float gf = gscale[b] * 2.0f * f;
+        float gq[3], gr[3];
+        prim_grad(kind, e, q, k0, k1, gf, gq, gr);
+        const float d[3] = {p[0] - e.c[0], p[1] - e.c[1], p[2] - e.c[2]};
 #pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                float gc = 0.f;
+        for (int i = 0; i < 3; ++i) {
+            float gc = 0.f;
 #pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    atomicAdd(acc + 3 + i * 3 + a, d[i] * gq[a]);  // q_a = sum_i V[i][a] d_i
-                    gc -= e.V[i * 3 + a] * gq[a];
-                }
-                atomicAdd(acc + 12 + i, gc);
+            for (int a = 0; a < 3; ++a) {
+                v[3 + i * 3 + a] = d[i] * gq[a];  // q_a = sum_i V[i][a] d_i
+                gc -= e.V[i * 3 + a] * gq[a];
             }
+            v[i] = gr[i];
+            v[12 + i] = gc;
         }
     }
+    slot_accumulate(s_acc, k, v);
     __syncthreads();
     for (int i = threadIdx.x; i < KM * 15; i += 256) {
         const float v = s_acc[i];
@@ -864,8 +886,12 @@ __global__ __launch_bounds__(256) void sample_nn_bwd_kernel(
     if (blockIdx.x * 256 >= total) return;
     for (int i = threadIdx.x; i < KM * 15; i += 256) s_acc[i] = 0.f;
     __syncthreads();
+    int k = -1;
+    float v[15];
+#pragma unroll
+    for (int j = 0; j < 15; ++j) v[j] = 0.f;
     if (s < total) {
-        int k = 0;
+        k = 0;
         while (k + 1 < KM && s >= off[k + 1]) ++k;
         const size_t sl = (size_t)b * KM + k;
         const float rk[3] = {r[sl * 3], r[sl * 3 + 1], r[sl * 3 + 2]};
@@ -880,19 +906,19 @@ __global__ __launch_bounds__(256) void sample_nn_bwd_kernel(
             const float p = Vk[i * 3] * e[0] + Vk[i * 3 + 1] * e[1] + Vk[i * 3 + 2] * e[2] + c[sl * 3 + i];
             gs[i] = gscale[b] * 2.0f * (p - t[i]);
         }
-        float *acc = s_acc + k * 15;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const float ge = Vk[j] * gs[0] + Vk[3 + j] * gs[1] + Vk[6 + j] * gs[2];  // (V^T g_s)[j]
-            atomicAdd(acc + j, ge * dir[j]);
+            v[j] = ge * dir[j];
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) atomicAdd(acc + 3 + i * 3 + j, gs[i] * e[j]);
-            atomicAdd(acc + 12 + i, gs[i]);
+            for (int j = 0; j < 3; ++j) v[3 + i * 3 + j] = gs[i] * e[j];
+            v[12 + i] = gs[i];
         }
     }
+    slot_accumulate(s_acc, k, v);
     __syncthreads();
     for (int i = threadIdx.x; i < KM * 15; i += 256) {
         const float v = s_acc[i];
