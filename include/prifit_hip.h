@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 400
+#define PRIFIT_ABI_VERSION 500
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -963,6 +963,16 @@ int prifit_adam_flat_alignment(void);
 int prifit_adam_flat(float *params, float *exp_avg, float *exp_avg_sq, const float *const *grads, const int32_t *offsets,
                      const int32_t *lengths, int nparams, long long total, const int32_t *step_in, int32_t *step_out, float lr,
                      float beta1, float beta2, float eps, float weight_decay, const int32_t *skip, void *stream);
+/* Momentum SGD in one launch over the same layout: train_partseg_shapenet.py:260-261 (torch.optim.SGD(lr, momentum=0.9)).  params,
+ * grads, offsets, lengths, nparams, total, step_in / step_out, skip and stream as in prifit_adam_flat (offsets multiples of
+ * prifit_adam_flat_alignment() floats); momentum_buf: ONE flat state buffer of `total` floats; NULL is accepted exactly when momentum == 0
+ * (then no state is read or written).  Arithmetic of torch/optim/sgd.py:_single_tensor_sgd in fp32: g += weight_decay * p; a parameter's
+ * first step (step_in == 0) sets buf = g without dampening, later ones buf = momentum * buf + (1 - dampening) * g; the update is
+ * g + momentum * buf with nesterov, buf without; p -= lr * g.  nesterov needs momentum > 0 and dampening == 0.  A NULL gradient
+ * or a non-zero skip leaves the parameter, its buffer and its count alone. */
+int prifit_sgd_flat(float *params, float *momentum_buf, const float *const *grads, const int32_t *offsets, const int32_t *lengths,
+                    int nparams, long long total, const int32_t *step_in, int32_t *step_out, float lr, float momentum,
+                    float dampening, float weight_decay, int nesterov, const int32_t *skip, void *stream);
 
 #ifdef __cplusplus
 }

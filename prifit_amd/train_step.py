@@ -3,6 +3,7 @@ train_partseg_shapenet.py:252-259, :321-340, :372-399, :436-451, :467-475 does a
 process per GPU.
 
     tr = Trainer(model)                       # Adam(lr, betas .9/.999, eps 1e-8, weight_decay) as upstream :252-259
+    tr = Trainer(model, optimizer="SGD")      # any other name: SGD(lr, momentum 0.9), upstream's `else:` at :260-261
     tr.set_epoch(epoch)                       # lr / BatchNorm-momentum schedule, upstream :325-334
     loss, acc = tr.supervised_step(points, target)              # upstream :372-399
     ss = tr.selfsup_step(chamfer_points, quantile=.05, ...)     # upstream :436-451
@@ -136,7 +137,7 @@ def graph_backbone(net, xyz, cls_label, fps_start):
 
 class Trainer:
     def __init__(self, model, num_part=50, learning_rate=0.001, decay_rate=1e-4, lr_decay=0.5, step_size=20, lmbda=1.0,
-                 fused_adam=True, strict_seen=False):
+                 fused_adam=True, strict_seen=False, optimizer="Adam"):
         # one process per GPU: this rank's own cores and capped CPU thread pools (prifit_amd/hostcfg.py; a single process is
         # left alone, and a launcher that already did it -- bench.py -- makes this a no-op)
         from . import hostcfg
@@ -147,7 +148,15 @@ class Trainer:
         # one launch per step over a flat parameter buffer on the GPU (prifit_amd/optim.py; PRIFIT_FLAT_ADAM=0 / fused_adam=False:
         # torch's optimizer, the A/B arm); host tensors (the gloo tests of the exchange logic) take torch's
         on_gpu = next(model.parameters()).is_cuda
-        if on_gpu and fused_adam and os.environ.get("PRIFIT_FLAT_ADAM", "1") != "0":
+        flat = on_gpu and fused_adam and os.environ.get("PRIFIT_FLAT_ADAM", "1") != "0"
+        if optimizer != "Adam":
+            # upstream :260-261: every other `--optimizer` is SGD(lr, momentum=0.9), without weight decay; the same flat / torch split
+            if flat:
+                from .optim import FlatSGD
+                self.optimizer = FlatSGD(model.parameters(), lr=learning_rate, momentum=0.9)
+            else:
+                self.optimizer = torch.optim.SGD(model.parameters(), lr=learning_rate, momentum=0.9)
+        elif flat:
             from .optim import FlatAdam
             self.optimizer = FlatAdam(model.parameters(), lr=learning_rate, betas=(0.9, 0.999), eps=1e-08, weight_decay=decay_rate)
         else:
@@ -179,7 +188,7 @@ class Trainer:
         if loss is not None:
             loss.backward()
         self.bucket.allreduce()
-        if hasattr(self.optimizer, "exp_avg"):           # FlatAdam: hand over the gradient list the exchange just read
+        if getattr(self.optimizer, "takes_grads", False):  # FlatAdam / FlatSGD: hand over the gradient list the exchange just read
             self.optimizer.step(grads=self.bucket.grads())
         else:
             self.optimizer.step()
