@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 500
+#define PRIFIT_ABI_VERSION 600
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -973,6 +973,25 @@ int prifit_adam_flat(float *params, float *exp_avg, float *exp_avg_sq, const flo
 int prifit_sgd_flat(float *params, float *momentum_buf, const float *const *grads, const int32_t *offsets, const int32_t *lengths,
                     int nparams, long long total, const int32_t *step_in, int32_t *step_out, float lr, float momentum,
                     float dampening, float weight_decay, int nesterov, const int32_t *skip, void *stream);
+
+/* ---- batch augmentation: one per-shape affine map, the layout change and the input subset in one launch.  Every augmentation
+ * of provider.py apart from jitter and dropout (rotate_*, random_scale / shift / anisotropic_scale: :46-147, :197-214, :240-262,
+ * :278-317) is a per-shape affine map of the first three channels; pretrain_partseg_shapenet.py:321-351 applies up to five of
+ * them, transposes to channels-first and gathers a random subset.
+ * src [B, M, C] channels-last, 3 <= C <= 8 (xyz, then channels that are copied unchanged: upstream touches [:, :, 0:3] only).
+ * affine [B, 12]: a row-major 3x3 matrix A, then t[3]; out_xyz = p . A + t (row vector times matrix, as np.dot(pc, R)).
+ * Every output is optional (NULL); at least one must be given:
+ *   dst_cl   [B, M, C]  channels-last (may be == src: in place)
+ *   dst_cf   [B, C, M]  channels-first (what the model and the loss take)
+ *   dst_sub  [B, C, n_subset] channels-first, column j = the transformed point subset[j]; subset [n_subset] int32 in [0, M)
+ * Fixed order, fp32, no fused multiply-add: o_j = ((p0*A[0][j] + p1*A[1][j]) + p2*A[2][j]) + t[j]; channels 3..C-1 are bit copies
+ * and dst_sub holds the bits of the matching dst_cf columns.  No atomics: the same inputs give the same bits in every run.  One
+ * launch; in place together with dst_sub takes two on the stream (the subset columns are read before the source is overwritten).
+ * The subset values are the caller's contract; a value outside [0, M) reads nothing and leaves NaN in its column.
+ * PRIFIT_EINVAL without a launch: B, M <= 0 (or B > 65535); C outside 3..8; all three outputs NULL; dst_sub without subset or with
+ * n_subset <= 0; dst_cf == src; src or affine NULL. */
+int prifit_affine_points(const float *src, int B, int M, int C, const float *affine, const int32_t *subset, int n_subset,
+                         float *dst_cl, float *dst_cf, float *dst_sub, void *stream);
 
 #ifdef __cplusplus
 }

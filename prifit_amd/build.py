@@ -37,6 +37,7 @@ SOURCES = {
     "chamfer.hip": ["-ffp-contract=off"],
     "atlas.hip": [],
     "optim.hip": [],
+    "augment.hip": ["-ffp-contract=off"],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],
     "comm.hip": [],        # host-only: the RCCL export (RCCL itself is resolved with dlopen at run time)

@@ -196,3 +196,61 @@ def three_interpolate_bwd(gout, col0, idx, weight, B, S, C):
     call("prifit_three_interpolate_bwd", ptr(gout), gout.stride(0), col0, ptr(idx), ptr(weight), B, N, S, C,
          ptr(dp2), cur_stream())
     return dp2
+
+
+def affine_points(src, affine, subset=None, want_cl=False, want_cf=False, out_cl=None):
+    """One per-shape affine map of the first three channels, the channels-first copy and the subset gather in ONE launch
+    (csrc/augment.hip; pretrain_partseg_shapenet.py:321-351: the provider.py augmentations, `.transpose(2, 1)`, and
+    `chamfer_points[:, :, choice]`).  src [B,M,C] float32 channels-last, 3 <= C <= 8; affine [B,12] float32 (A row-major, then t;
+    out = p . A + t) on the host or on the device; subset: indices into [0, M) -- numpy / a host tensor is checked here and
+    uploaded TOGETHER with a host `affine` in one copy, a device tensor is taken as it is (the caller's contract).
+    -> (cl [B,M,C] | None, cf [B,C,M] | None, sub [B,C,len(subset)] | None); out_cl: the tensor to write cl into (may be `src`:
+    in place; implies want_cl)."""
+    require_cuda(src)
+    if src.dtype != torch.float32 or src.dim() != 3 or not src.is_contiguous():
+        raise ValueError("affine_points: src must be a contiguous float32 [B,M,C] tensor")
+    B, M, C = src.shape
+    dev = src.device
+    if out_cl is not None:
+        want_cl = True
+        if out_cl.shape != src.shape or out_cl.dtype != torch.float32 or not out_cl.is_cuda or not out_cl.is_contiguous():
+            raise ValueError("affine_points: out_cl must be a contiguous float32 device tensor of src's shape")
+    if not (want_cl or want_cf or subset is not None):
+        raise ValueError("affine_points: no output requested")
+    n_sub, sub_dev = 0, None
+    if subset is not None and not (torch.is_tensor(subset) and subset.is_cuda):
+        subset = np.ascontiguousarray(subset.numpy() if torch.is_tensor(subset) else subset)
+        if subset.ndim != 1 or subset.size == 0 or subset.dtype.kind not in "iu":
+            raise ValueError("affine_points: subset must be a non-empty 1-d integer array")
+        if int(subset.min()) < 0 or int(subset.max()) >= M:
+            raise IndexError("affine_points: subset index outside [0, %d)" % M)
+        n_sub = subset.size
+    elif subset is not None:
+        if subset.dim() != 1 or subset.numel() == 0:
+            raise ValueError("affine_points: subset must be a non-empty 1-d integer tensor")
+        n_sub = subset.numel()
+        sub_dev = subset.to(torch.int32).contiguous()
+    if torch.is_tensor(affine) and affine.is_cuda:
+        aff_dev = cf(affine)
+        if n_sub and sub_dev is None:
+            sub_dev = torch.from_numpy(subset.astype(np.int32)).to(dev)
+    else:
+        aff = np.ascontiguousarray(affine.numpy() if torch.is_tensor(affine) else affine, dtype=np.float32)
+        if n_sub and sub_dev is None:
+            # matrices and indices in one buffer of 32-bit words: one host-to-device copy
+            words = np.empty(B * 12 + n_sub, dtype=np.float32)
+            words[:B * 12] = aff.reshape(-1)
+            words[B * 12:].view(np.int32)[:] = subset
+            up = torch.from_numpy(words).to(dev)
+            aff_dev, sub_dev = up[:B * 12], up[B * 12:].view(torch.int32)
+        else:
+            aff_dev = torch.from_numpy(aff).to(dev)
+    if aff_dev.numel() != B * 12:
+        raise ValueError("affine_points: affine must hold [B,12] floats")
+    cl = (out_cl if out_cl is not None else torch.empty_like(src)) if want_cl else None
+    cfirst = torch.empty(B, C, M, dtype=torch.float32, device=dev) if want_cf else None
+    sub = torch.empty(B, C, n_sub, dtype=torch.float32, device=dev) if n_sub else None
+    with profiler.span("affine_points", 4.0 * B * C * (M * (1 + bool(want_cl) + bool(want_cf)) + 2 * n_sub)):
+        call("prifit_affine_points", ptr(src), B, M, C, ptr(aff_dev), ptr(sub_dev), n_sub, ptr(cl), ptr(cfirst), ptr(sub),
+             cur_stream())
+    return cl, cfirst, sub

@@ -7,6 +7,8 @@ process per GPU.
     tr.set_epoch(epoch)                       # lr / BatchNorm-momentum schedule, upstream :325-334
     loss, acc = tr.supervised_step(points, target)              # upstream :372-399
     ss = tr.selfsup_step(chamfer_points, quantile=.05, ...)     # upstream :436-451
+    ss = tr.selfsup_step(chamfer_points, rotation_z=True, ...)  # + the augmentation flags of pretrain_partseg_shapenet.py:321-351
+    val = tr.selfsup_validate(val_batches, ...)                 # its per-epoch validation pass, :377-402
     tr.save(path) / tr.load(path)             # checkpoint dict of upstream :467-475
     tr.finish()                               # REQUIRED after the last step under torch.distributed: the deferred
                                               # has-gradient check of the final exchange (ddp.FlatGradBucket.flush)
@@ -214,9 +216,32 @@ class Trainer:
         return loss.detach(), acc
 
     # ------------------------------------------------------------------ self-supervised step (upstream :436-451)
-    def _selfsup_batch(self, chamfer_points, npoint, augment, subset):
-        """Augmentation + the random `npoint`-subset that is the model input (upstream :439-441), channels-first."""
+    def _selfsup_batch(self, chamfer_points, npoint, augment, subset, rotation_z=False, rotation_z_45=False,
+                       random_anisotropic_scale=False, fused_augment=False):
+        """Augmentation + the random `npoint`-subset that is the model input (upstream :439-441), channels-first.
+
+        With one of the four flags set this is the batch preparation of pretrain_partseg_shapenet.py:321-351 -- its
+        `--rotation_z`, `--rotation_z_45`, `--random_anisotropic_scale` (args_parser.py) and, with fused_augment alone, just scale
+        and shift -- as ONE 3x4 matrix per shape and ONE launch (provider.compose_affine / affine_batch, csrc/augment.hip).  The
+        parameters are drawn on the host with `np.random`, each by the reference function's own call and in the script's order
+        for its `chamfer_points` array: scale (B), shift (B,3), anisotropic scale (B,1,3), one `uniform()` angle per shape, one
+        `randint(1, 8)` per shape, then `choice(M, npoint, replace=False)`.  The draws the script spends on its `points` array
+        (:319-320, :324, :332, :336) are NOT made: that array is overwritten by the subset of `chamfer_points` at :351, so a seeded
+        run follows the script's law, not its `np.random` stream position."""
         B, M, _ = chamfer_points.shape
+        if rotation_z or rotation_z_45 or random_anisotropic_scale or fused_augment:
+            if not augment:
+                raise ValueError("rotation_z / rotation_z_45 / random_anisotropic_scale / fused_augment are augmentations: "
+                                 "they cannot be combined with augment=False")
+            from . import provider
+            scale = np.random.uniform(0.8, 1.25, B)                                                   # provider.py:300
+            shift = np.random.uniform(-0.1, 0.1, (B, 3))                                              # :286
+            aniso = np.random.uniform(0.8, 1.25, [B, 1, 3]) if random_anisotropic_scale else None     # :314
+            ang1 = np.array([np.random.uniform() * 2 * np.pi for _ in range(B)]) if rotation_z else None      # :97
+            ang2 = np.array([np.random.randint(1, 8) * np.pi / 4 for _ in range(B)]) if rotation_z_45 else None   # :118
+            if subset is None:
+                subset = np.random.choice(M, npoint, replace=False)
+            return provider.affine_batch(chamfer_points, provider.compose_affine(scale, shift, aniso, ang1, ang2), subset)
         if augment:
             chamfer_points = random_scale_shift(chamfer_points)
         cham = chamfer_points.transpose(2, 1).contiguous()
@@ -224,17 +249,19 @@ class Trainer:
             subset = torch.from_numpy(np.random.choice(M, npoint, replace=False)).to(cham.device)
         return cham, cham[:, :, subset].contiguous()
 
-    def prefetch_selfsup(self, chamfer_points, npoint=2048, augment=True, subset=None, fps_start=None):
+    def prefetch_selfsup(self, chamfer_points, npoint=2048, augment=True, subset=None, fps_start=None, rotation_z=False,
+                         rotation_z_45=False, random_anisotropic_scale=False, fused_augment=False):
         """Prepare the NEXT self-supervised batch now -- augmentation and subset, what a DataLoader worker does upstream --
         and start its farthest-point sampling behind the backbone forward of the step that runs next (`model.sample_ahead`
         through the `after_backbone` hook: the sampling chain depends on the coordinates alone, is 640 serial rounds on one
         workgroup per shape, and there it runs beside the matrix-bound mean-shift kernels instead of at the head of its
         own step; same indices as in-line sampling).  The following `selfsup_step()` WITHOUT `chamfer_points` consumes it.
-        Models without `sample_ahead` (DGCNN) only get the batch prepared."""
+        Models without `sample_ahead` (DGCNN) only get the batch prepared.  The four augmentation flags: `_selfsup_batch`."""
         if self._next is not None:
             raise RuntimeError("prefetch_selfsup: the batch of an earlier prefetch has not been consumed by a "
                                "selfsup_step() yet -- a second prefetch would drop it (its augmentation and RNG draw spent)")
-        cham, points = self._selfsup_batch(chamfer_points, npoint, augment, subset)
+        cham, points = self._selfsup_batch(chamfer_points, npoint, augment, subset, rotation_z, rotation_z_45,
+                                           random_anisotropic_scale, fused_augment)
         nxt = {"cham": cham, "points": points, "ahead": None, "fps_start": fps_start}
         self._next = nxt
         if points.is_cuda and hasattr(self.model, "sample_ahead"):
@@ -245,9 +272,12 @@ class Trainer:
             self.model.after_backbone = hook
 
     def selfsup_step(self, chamfer_points=None, npoint=2048, quantile=0.01, msc_iterations=20, max_num_clusters=25,
-                     augment=True, subset=None, **loss_kwargs):
+                     augment=True, subset=None, rotation_z=False, rotation_z_45=False, random_anisotropic_scale=False,
+                     fused_augment=False, **loss_kwargs):
         """chamfer_points [B,M,3]: the model input is a random `npoint`-subset of them (upstream :441).
-        chamfer_points=None: the batch prepared by `prefetch_selfsup`."""
+        chamfer_points=None: the batch prepared by `prefetch_selfsup` (the flags then belong to that call).
+        rotation_z / rotation_z_45 / random_anisotropic_scale: the pre-training script's augmentation flags, fused_augment: the
+        one-launch preparation for scale and shift alone -- see `_selfsup_batch`; all off: the torch-operator path."""
         if chamfer_points is None:
             if self._next is None:
                 raise RuntimeError("selfsup_step() without chamfer_points needs a prefetch_selfsup(...) before it")
@@ -259,7 +289,8 @@ class Trainer:
             if start is not None:
                 loss_kwargs = dict(loss_kwargs, fps_start=start)
         else:
-            cham, points = self._selfsup_batch(chamfer_points, npoint, augment, subset)
+            cham, points = self._selfsup_batch(chamfer_points, npoint, augment, subset, rotation_z, rotation_z_45,
+                                               random_anisotropic_scale, fused_augment)
         B = cham.shape[0]
         category_label = torch.zeros(B, 1, 16, device=cham.device)
         self.bucket.zero()
@@ -279,6 +310,32 @@ class Trainer:
         self._apply(None)
         return ss_loss.detach()
 
+    # ------------------------------------------------------------------ validation (pretrain_partseg_shapenet.py:377-402)
+    def selfsup_validate(self, batches, npoint=2048, quantile=0.01, msc_iterations=20, max_num_clusters=25, subset=None,
+                         **loss_kwargs):
+        """The per-epoch validation pass of the pre-training script (:379-401): the model in eval mode under no_grad, no
+        augmentation, per batch [B,M,3] a random `npoint`-subset (`np.random.choice`, or `subset` for every batch when given)
+        as the model input; returns the mean over the batches of mean(out[3]) as a Python float (the script's `avg_val_loss`).
+        No optimizer step, no gradient exchange -- local to this rank; the model goes back into the mode it was in.  As
+        upstream, every forward with the convex loss advances the model's entropy-weight schedule (`beta *= 0.99`)."""
+        was_training = self.model.training
+        self.model.eval()
+        total, count = 0.0, 0
+        try:
+            with torch.no_grad():
+                for chamfer_points in batches:
+                    cham, points = self._selfsup_batch(chamfer_points, npoint, False, subset)
+                    category_label = torch.zeros(cham.shape[0], 1, 16, device=cham.device)
+                    out = self.model(points, category_label, chamfer_points=cham, include_convex_loss=True, quantile=quantile,
+                                     msc_iterations=msc_iterations, max_num_clusters=max_num_clusters, **loss_kwargs)
+                    total += torch.mean(out[3]).item()
+                    count += 1
+        finally:
+            self.model.train(was_training)
+        if count == 0:
+            raise ValueError("selfsup_validate: no batches")
+        return total / count
+
     # ------------------------------------------------------------------ checkpoints (upstream :467-475, :263-274)
     def finish(self):
         """After the last optimizer step: the deferred has-gradient check of the final exchange (ddp.FlatGradBucket.flush)."""
@@ -291,12 +348,17 @@ class Trainer:
         self.bucket.flush()
         self.bucket.sync_buffers(0)
 
-    def write_checkpoint(self, path):
-        """Local, no communication: the checkpoint dict of upstream :467-475 -- safe under `if rank == 0:`."""
-        torch.save({"epoch": self.epoch, "train_acc": self.train_acc, "model_state_dict": self.model.state_dict(),
-                    "optimizer_state_dict": self.optimizer.state_dict()}, path)
+    def write_checkpoint(self, path, extra=None):
+        """Local, no communication: the checkpoint dict of upstream :467-475 -- safe under `if rank == 0:`.  extra: a dict
+        merged into it, e.g. the `selfsup_loss` / `val_loss` keys of the pre-training script's checkpoints
+        (pretrain_partseg_shapenet.py:431-437)."""
+        state = {"epoch": self.epoch, "train_acc": self.train_acc, "model_state_dict": self.model.state_dict(),
+                 "optimizer_state_dict": self.optimizer.state_dict()}
+        if extra is not None:
+            state.update(extra)
+        torch.save(state, path)
 
-    def save(self, path):
+    def save(self, path, extra=None):
         """sync_buffers() + write_checkpoint() on rank 0.  COLLECTIVE under torch.distributed: EVERY rank must call it
         (a caller that guards it with `if rank == 0:` would leave rank 0 alone in the broadcast -- such a caller uses
         write_checkpoint, after a sync_buffers() that all ranks entered)."""
@@ -305,7 +367,7 @@ class Trainer:
         self.sync_buffers()
         if dist.is_initialized() and dist.get_rank() != 0:
             return
-        self.write_checkpoint(path)
+        self.write_checkpoint(path, extra)
 
     def load(self, path):
         ck = torch.load(path, map_location="cpu")
