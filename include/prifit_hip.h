@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 600
+#define PRIFIT_ABI_VERSION 700
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -992,6 +992,27 @@ int prifit_sgd_flat(float *params, float *momentum_buf, const float *const *grad
  * n_subset <= 0; dst_cf == src; src or affine NULL. */
 int prifit_affine_points(const float *src, int B, int M, int C, const float *affine, const int32_t *subset, int n_subset,
                          float *dst_cl, float *dst_cf, float *dst_sub, void *stream);
+
+/* ---- part-segmentation metrics of testing.py:139-204 in one launch: the category-restricted arg-max of every point and the
+ * integer counts behind accuracy, class-average accuracy and the per-shape IoU.  One pass over the scores, integer atomics
+ * only (32-bit into inter / uni, 64-bit into totals): the same bits in every run, equal to a numpy restatement.
+ * scores: B * N rows of P <= 64 fp32 part scores, row stride ld >= P floats (columns P .. ld - 1 are never read);
+ * target [B, N] int64 part labels; cat_of_label [P] int32 = the category of each part, -1 = none.
+ * The category of shape b is cat_of_label[target[b, 0]] (testing.py:142) -> shape_cat [B] (-1 where that is undefined).
+ * restricted != 0: pred = the FIRST index of the maximum score among the parts of the shape's category, np.argmax(logits[:,
+ *   parts]) + parts[0] of :143-144; restricted == 0: over all P parts.  numpy's order: a NaN beats every number and the first
+ *   NaN wins, -0 == +0, a row whose allowed scores are all -inf gives the first allowed part.  pred [B, N] int64, may be NULL.
+ * inter [B, P] += rows of shape b with pred == l and target == l; uni [B, P] += rows with pred == l or target == l: both
+ *   int32 and ZEROED BY THE CALLER (the workgroups of a shape add to them in any order).
+ * totals [2 + 2 P] int64, ACCUMULATED over calls: [0] correct (pred == target), [1] bad, [2 .. 2 + P) seen_class[target],
+ *   [2 + P .. 2 + 2 P) correct_class[target] (:166-174).
+ * bad: a row whose label is outside [0, P), and in restricted mode every row of a shape whose first label is outside [0, P) or
+ *   has category -1 (the reference stops with a KeyError).  Such a row adds 1 to totals[1] and to nothing else; its pred is
+ *   still the arg-max (-1 where the shape has no category).  Nothing is read or written out of range.
+ * PRIFIT_EINVAL without a launch: P < 1 or P > 64, ld < P, B or N <= 0, a NULL pointer other than pred. */
+int prifit_seg_metrics(const float *scores, long long ld, const long long *target, int B, int N, int P,
+                       const int32_t *cat_of_label, int restricted, long long *pred, int32_t *shape_cat, int32_t *inter,
+                       int32_t *uni, long long *totals, void *stream);
 
 #ifdef __cplusplus
 }

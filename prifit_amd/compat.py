@@ -6,7 +6,7 @@
 After `install()` the names the reference's trainer / loss import -- `models.pointnet_util`,
 `models.pointnet2_part_seg_msg`, `models.pretrain_pointnet2_part_seg_msg`, `models.reconstruction`, `convex_loss`,
 `src.mean_shift`, `src.ellipsoid_fitting`, `src.ellipsoid_utils`, `src.fitting_utils`, `src.sample_ellipsoid`, `src.utils`,
-`src.guard`, `src.VisUtils`, `data_utils.ShapeNetDataLoader`, `provider`, `testing` -- are this package's modules, and every
+`src.guard`, `src.VisUtils`, `src.eval_utils`, `data_utils.ShapeNetDataLoader`, `provider`, `testing` -- are this package's modules, and every
 name `train_partseg_shapenet.py:5-28`, `testing.py:1-30` and `fitting.py:1-18` import from them resolves with the
 reference's signature (tests/test_compat_imports.py holds the list).  What stays the reference's own: `args_parser` (its CLI)
 and its third-party imports (tensorboard_logger, ipdb, tqdm, open3d, trimesh).
@@ -38,6 +38,7 @@ _ALIASES = {
     "src.VisUtils": "prifit_amd.src.utils",          # fitting.py:2 imports visualize_point_cloud from it
     "src.guard": "prifit_amd.src.guard",
     "src.dgcnn": "prifit_amd.src.dgcnn",
+    "src.eval_utils": "prifit_amd.src.eval_utils",
 }
 
 

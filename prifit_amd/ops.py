@@ -254,3 +254,46 @@ def affine_points(src, affine, subset=None, want_cl=False, want_cf=False, out_cl
         call("prifit_affine_points", ptr(src), B, M, C, ptr(aff_dev), ptr(sub_dev), n_sub, ptr(cl), ptr(cfirst), ptr(sub),
              cur_stream())
     return cl, cfirst, sub
+
+
+def seg_metrics(scores, target, cat_of_label, restricted=True, totals=None, out=None):
+    """The part-segmentation counts of testing.py:139-204 in ONE launch, nothing read back (csrc/seg_metrics.hip).
+    scores [B,N,P] float32 part scores, P <= 64 (a view with a row stride >= P is taken as it is); target [B,N] int64 labels;
+    cat_of_label [P] int32 DEVICE tensor, the category of each part (-1 = none).  restricted: the arg-max runs over the parts of
+    the shape's category (that of its first label) only, first maximum, numpy's NaN order; False: over all P parts.
+    totals: int64 [2 + 2 P] device tensor to ACCUMULATE into -- correct, bad, seen_class [P], correct_class [P] -- or None for a
+    fresh zeroed one; bad counts the rows whose label (or, restricted, whose shape's first label) has no part / category: the
+    caller turns it into an error.  out: optional (pred | None, shape_cat, inter, uni) to write into, inter and uni ZEROED by
+    the caller.  -> (pred [B,N] int64, shape_cat [B] int32, inter [B,P] int32, uni [B,P] int32, totals)."""
+    require_cuda(scores, target, cat_of_label)
+    if scores.dim() != 3 or scores.dtype != torch.float32:
+        raise ValueError("seg_metrics: scores must be a float32 [B,N,P] tensor")
+    B, N, P = scores.shape
+    if P > 64 or B * N == 0:
+        raise ValueError("seg_metrics: needs 1 <= P <= 64 parts and at least one point, got %s" % (tuple(scores.shape),))
+    if scores.stride(2) != 1 or scores.stride(1) < P or (B > 1 and scores.stride(0) != N * scores.stride(1)):
+        scores = scores.contiguous()
+    if tuple(target.shape) != (B, N):
+        raise ValueError("seg_metrics: target must be [B,N] = %s, got %s" % ((B, N), tuple(target.shape)))
+    target = target.long().contiguous()
+    if cat_of_label.dtype != torch.int32 or cat_of_label.numel() != P or not cat_of_label.is_contiguous():
+        raise ValueError("seg_metrics: cat_of_label must be a contiguous int32 [P] tensor")
+    dev = scores.device
+    if totals is None:
+        totals = torch.zeros(2 + 2 * P, dtype=torch.int64, device=dev)
+    elif totals.dtype != torch.int64 or totals.numel() != 2 + 2 * P or not totals.is_cuda or not totals.is_contiguous():
+        raise ValueError("seg_metrics: totals must be a contiguous int64 [2 + 2 P] device tensor")
+    if out is None:
+        pred = torch.empty(B, N, dtype=torch.int64, device=dev)
+        counts = zero_pool.zeros(B * (1 + 2 * P), device=dev).view(torch.int32)     # zero bits: one fill for the three
+        shape_cat, inter, uni = counts[:B], counts[B:B + B * P].view(B, P), counts[B + B * P:].view(B, P)
+    else:
+        pred, shape_cat, inter, uni = out
+        for name, t, dt, shp in (("pred", pred, torch.int64, (B, N)), ("shape_cat", shape_cat, torch.int32, (B,)),
+                                 ("inter", inter, torch.int32, (B, P)), ("uni", uni, torch.int32, (B, P))):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != shp or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("seg_metrics: out %s must be a contiguous %s %s device tensor" % (name, dt, shp))
+    with profiler.span("seg_metrics", 4.0 * B * N * P):
+        call("prifit_seg_metrics", ptr(scores), scores.stride(1), ptr(target), B, N, P, ptr(cat_of_label), int(bool(restricted)),
+             ptr(pred), ptr(shape_cat), ptr(inter), ptr(uni), ptr(totals), cur_stream())
+    return pred, shape_cat, inter, uni, totals

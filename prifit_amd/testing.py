@@ -11,7 +11,11 @@
 Rules kept from the reference: the category of a shape is that of its first target label (:142); the prediction
 is the arg-max over that category's parts only (:143-144); a part absent from both prediction and target counts
 as IoU 1 (:203-204); a shape's IoU is the mean over its category's parts; class_avg_iou averages the per-category
-means, instance_avg_iou averages all shapes (:226-240)."""
+means, instance_avg_iou averages all shapes (:226-240).
+
+On the device the counts behind all of that come from ONE kernel launch per batch (csrc/seg_metrics.hip): update()
+copies nothing to the host and does not synchronise, compute() makes a single transfer.  A label without a part, or a shape
+whose first label has no category -- where the reference stops with a KeyError -- makes compute() raise ValueError."""
 import importlib
 import os
 
@@ -32,22 +36,33 @@ def to_categorical(y, num_classes):
 
 
 class SegmentationEvaluator:
-    def __init__(self, num_part=50, categories=None):
+    """fused=True (default): float32 device logits with at most 64 parts are counted by one kernel launch per batch
+    (ops.seg_metrics) and nothing is read back before compute(); fused=False, the CPU and every other input keep the torch path."""
+    _SLAB_SHAPES = 1024          # shapes per zeroed count buffer of the kernel path (one fill per that many, not one per batch)
+
+    def __init__(self, num_part=50, categories=None, fused=True):
         self.categories = categories if categories is not None else seg_classes
         self.names = list(self.categories.keys())
         self.num_part = num_part
+        self.fused = fused
         cat_of_label = torch.full((num_part,), -1, dtype=torch.long)
         for ci, name in enumerate(self.names):
             cat_of_label[self.categories[name]] = ci
         self.cat_of_label = cat_of_label
+        self._table = None                                  # its int32 device copy, uploaded on the first device seen
         self.reset()
 
     def reset(self):
         self.correct = 0
         self.seen = 0
+        self.bad = 0
         self.seen_class = torch.zeros(self.num_part, dtype=torch.long)
         self.correct_class = torch.zeros(self.num_part, dtype=torch.long)
         self.shape_iou, self.shape_cat = [], []
+        # kernel path: the running totals, the zeroed count buffers batches are carved from ([buffer, words used]), and per
+        # batch (its place in shape_iou / shape_cat, its buffer's number, its first word, B): compute() folds them into the
+        # fields above, which hold the kernel path's share only after that
+        self._totals, self._slabs, self._pending = None, [], []
 
     @torch.no_grad()
     def predict(self, seg_pred, target):
@@ -60,6 +75,8 @@ class SegmentationEvaluator:
     @torch.no_grad()
     def update(self, seg_pred, target):
         B, N, P = seg_pred.shape
+        if self.fused and seg_pred.is_cuda and seg_pred.dtype == torch.float32 and P == self.num_part and P <= 64 and B * N:
+            return self._update_fused(seg_pred, target)
         target = target.long()
         pred, cat = self.predict(seg_pred, target)
         hit = pred == target
@@ -77,7 +94,66 @@ class SegmentationEvaluator:
         self.shape_cat.append(cat.cpu())
         return pred
 
+    def _update_fused(self, seg_pred, target):
+        """One launch, no device-to-host copy, no synchronisation: the batch's shape_cat [B], inter and uni [B,P] stay on the
+        device in a zeroed buffer shared by many batches, the batch totals are added to one persistent tensor."""
+        from . import ops
+        B, N, P = seg_pred.shape
+        dev = seg_pred.device
+        if self._totals is not None and self._totals.device != dev:
+            self._fold()
+        if self._table is None or self._table.device != dev:
+            self._table = self.cat_of_label.to(torch.int32).to(dev)
+        if self._totals is None:
+            self._totals = torch.zeros(2 + 2 * P, dtype=torch.int64, device=dev)
+        words = B * (1 + 2 * P)
+        if not self._slabs or self._slabs[-1][1] + words > self._slabs[-1][0].numel():
+            self._slabs.append([torch.zeros(max(self._SLAB_SHAPES, 4 * B) * (1 + 2 * P), dtype=torch.int32, device=dev), 0])
+        slab, off = self._slabs[-1]
+        w = slab[off:off + words]
+        pred = torch.empty(B, N, dtype=torch.int64, device=dev)
+        ops.seg_metrics(seg_pred, target, self._table, True, self._totals,
+                        out=(pred, w[:B], w[B:B + B * P].view(B, P), w[B + B * P:].view(B, P)))
+        self._pending.append((len(self.shape_iou), len(self._slabs) - 1, off, B))
+        self._slabs[-1][1] = off + words
+        self.shape_iou.append(None)                          # this batch's place in the order of the shapes
+        self.shape_cat.append(None)
+        self.seen += B * N
+        return pred
+
+    def _fold(self):
+        """The single transfer of the kernel path: the totals and every pending batch's counts in one copy; from the integer
+        counts the float64 per-shape IoU of testing.py:176-204 (np.mean over the category's parts, an absent part = 1)."""
+        if self._totals is None:
+            return
+        P = self.num_part
+        host = torch.cat([self._totals.view(torch.int32)] + [slab[:used] for slab, used in self._slabs]).cpu().numpy()
+        totals = host[:2 * (2 + 2 * P)].view(np.int64)
+        first = np.cumsum([2 * (2 + 2 * P)] + [used for _, used in self._slabs])       # first word of every buffer in `host`
+        col = self.cat_of_label.numpy()
+        for place, k, off, B in self._pending:
+            w = host[first[k] + off:first[k] + off + B * (1 + 2 * P)]
+            cat = w[:B].astype(np.int64)
+            inter = w[B:B + B * P].reshape(B, P).astype(np.float64)
+            union = w[B + B * P:].reshape(B, P).astype(np.float64)
+            part_iou = np.where(union == 0, 1.0, inter / np.maximum(union, 1.0))
+            iou = np.full(B, np.nan)                          # (a shape without a category: nan, as the torch path's 0 / 0)
+            for ci in np.unique(cat[cat >= 0]):
+                rows = np.nonzero(cat == ci)[0]
+                iou[rows] = np.mean(np.ascontiguousarray(part_iou[np.ix_(rows, np.nonzero(col == ci)[0])]), axis=1)
+            self.shape_iou[place] = torch.from_numpy(iou)
+            self.shape_cat[place] = torch.from_numpy(cat)
+        self.correct += int(totals[0])
+        self.bad += int(totals[1])
+        self.seen_class += torch.from_numpy(totals[2:2 + P].copy())
+        self.correct_class += torch.from_numpy(totals[2 + P:].copy())
+        self._totals, self._slabs, self._pending = None, [], []
+
     def compute(self):
+        self._fold()
+        if self.bad:
+            raise ValueError("SegmentationEvaluator: %d point(s) carry a label outside [0, %d) or belong to a shape whose first "
+                             "label has no category (the reference stops with a KeyError)" % (self.bad, self.num_part))
         iou = torch.cat(self.shape_iou) if self.shape_iou else torch.zeros(0, dtype=torch.float64)
         cat = torch.cat(self.shape_cat) if self.shape_cat else torch.zeros(0, dtype=torch.long)
         per_cat = {}
@@ -162,11 +238,11 @@ def evaluate_loader(classifier, loader, num_classes=16, num_part=50, category=Tr
         out = classifier(points, to_categorical(label, num_classes), include_convex_loss=False, evaluation=True, **forward_kwargs)
         seg_pred = out[0]
         if len(out) >= 5 and torch.is_tensor(out[4]):
-            chamfer.append(float(out[4].float().mean()))
+            chamfer.append(out[4].float().mean())             # a device scalar: read back with the others, after the loop
         ev.update(seg_pred, target)
     classifier.train(was_training)
     test_metrics = ev.compute()
-    test_metrics['chamfer_loss'] = float(np.mean(chamfer)) if chamfer else 0.0
+    test_metrics['chamfer_loss'] = float(np.mean(torch.stack(chamfer).cpu().double().numpy())) if chamfer else 0.0
     if metrics:
         if metrics['best_class_avg_miou'] <= test_metrics['class_avg_iou']:
             metrics.update(best_chamfer_loss=test_metrics['chamfer_loss'], best_epoch=epoch + 1,
