@@ -9,8 +9,8 @@ src/ellipsoid_utils.py:19-27).  Reference sites are cited per function (paths re
 import contextlib
 import ctypes
 import os
-
 import time
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -25,6 +25,45 @@ KM_MAX = 64      # ... and up to 64 when the caller raises --max_num_clusters (a
                  # gaurd_mean_shift accepts 49, src/mean_shift.py:212-226): every kernel takes the slot count at run time
 NMS_CAP = 64     # centre ids kept by nms before the cluster-count check
 SAMPLE_CAP = 13312  # >= 10000 + KM * 100 surface samples per shape (src/ellipsoid_utils.py:105-106); sample_cap(K)
+
+# The switches of the mean-shift clustering path (A/B arms; which route each one selects: DESIGN 3.8).  The route functions
+# below read them at every call; a backward follows the route its forward stored.
+# mean-shift backward engine: "hybrid" (default) | "gemm" | "fused", see _dense_bwd_route
+BWD_MODE = os.environ.get("PRIFIT_MS_BWD", "hybrid")
+# 1: dX from the stream-fed flash-style kernel (prifit_meanshift_dx_streams: no split-K atomics, so dX is bit-reproducible
+# from run to run) instead of the dual-source GEMM; measured 456 vs ~440 us per call at B = 24, N = 2048 -> default off
+DX_STREAMS = os.environ.get("PRIFIT_MS_DX_STREAMS", "0") != "0"
+# stream-K schedule of the dense backward's dZ kernel (grid = resident slots, split query blocks combine through atomics):
+# +7 % (488 -> 452 us at B = 24, N = 2048).  (The forward's time is linear in its block count: no such schedule there.)
+MS_BALANCED = True
+CHORD_SYM = os.environ.get("PRIFIT_CHORD_SYM", "1") != "0"   # symmetric kernel for chord_matrix(X, X)
+FUSE_NMS_OWNER = True   # nms: the owner pass (column argmin) in the chord kernel's epilogue (False: a second read of the matrix)
+# cluster(): the loss reads the shifted points through `center = new_X[indices]` only, so the mean-shift backward runs
+# on those rows alone (MeanShiftRowsFn); 0 = the dense backward of MeanShiftFn + a gather (same numbers; the A/B arm
+# and the path of callers that differentiate through the whole of new_X)
+ROWS_BWD = os.environ.get("PRIFIT_MS_ROWS", "1") != "0"
+# LABELLED EXPERIMENT, default off: the two products of the mean-shift FORWARD on the 16-bit matrix pipe with
+# error-compensated operands (csrc/meanshift_split.hip): "bf16x3" | "bf16x6" | "fp16x3".  D = 128, N % 256 == 0, and only
+# where the kernel matrix is not kept (the row-sparse backward, i.e. cluster()); anything else takes the fp32 kernels.
+# A number measured with it on is not an fp32 number: bench.py labels it (`dtype`, `experiment`) and never reports it as
+# the headline.
+MS_SPLIT = os.environ.get("PRIFIT_MS_SPLIT", "0")
+_SPLIT_MODES = {"bf16x3": 1, "bf16x6": 2, "fp16x3": 3}
+split_launches = 0   # updates that took the experiment's kernel (tests assert on it; nothing reads it in the product)
+# The first mean-shift update of a trajectory reads the chord matrix the bandwidth step has just written instead of forming
+# S = X X^T again (csrc/meanshift_fused.hip, SLOAD: Z_0 = X, one of the 20 N x N x D products of ten updates gone).  0: every
+# update takes the standard kernel (A/B arm, tested against this one).
+MS_FIRST_CHORD = os.environ.get("PRIFIT_MS_FIRST_CHORD", "1") != "0"
+# How the row-sparse backward runs its T iterations (csrc/meanshift_rows.hip, prifit_meanshift_rows_bwd `mode`):
+#   2  one workgroup per live row runs all T iterations of that row (nothing crosses workgroups): 2 launches;
+#   1  key-tiled iterations as ONE launch over a work queue: 3 launches;  0  one launch per iteration: T + 2 launches.
+# "auto": 2 up to 32 cluster slots per shape (the loss path: ~8 live rows per shape, 148 us against 198 / 221 at B = 24), 1 above
+# (many live rows: the key-tiled forms read the dictionary once for all rows).  profiles/r06_ms_rows.txt.
+MS_ROWS_MODE = os.environ.get("PRIFIT_MS_ROWS_MODE", "auto")
+# nms reads ONE BIT per element of its chord matrix once the owner pass is fused into the kernel that forms it: the matrix is
+# then never written (csrc/gemm.hip chord_sym_kernel MODE 2: 12.6 MB of mask instead of 403 MB at B = 24, N = 2048).  0: the
+# float matrix (A/B arm, tested equal).
+NMS_MASK = os.environ.get("PRIFIT_NMS_MASK", "1") != "0"
 
 
 def slots_for(max_num_clusters):
@@ -41,28 +80,6 @@ def slots_for(max_num_clusters):
 def sample_cap(K):
     """Surface-sample slots per shape for K cluster slots: 10000 + 100 K (src/ellipsoid_utils.py:105-106), in blocks of 256."""
     return SAMPLE_CAP if K <= KM else (10000 + 100 * K + 255) // 256 * 256
-# mean-shift backward engine: "hybrid" (default) | "gemm" | "fused", see MeanShiftFn.backward
-BWD_MODE = __import__("os").environ.get("PRIFIT_MS_BWD", "hybrid")
-# 1: dX from the stream-fed flash-style kernel (prifit_meanshift_dx_streams: no split-K atomics, so dX is bit-reproducible
-# from run to run) instead of the dual-source GEMM; measured 456 vs ~440 us per call at B = 24, N = 2048 -> default off
-DX_STREAMS = __import__("os").environ.get("PRIFIT_MS_DX_STREAMS", "0") != "0"
-# stream-K schedule of the dense backward's dZ kernel (grid = resident slots, split query blocks combine through atomics):
-# +7 % (488 -> 452 us at B = 24, N = 2048).  (The forward's time is linear in its block count: no such schedule there.)
-MS_BALANCED = True
-CHORD_SYM = __import__("os").environ.get("PRIFIT_CHORD_SYM", "1") != "0"   # symmetric kernel for chord_matrix(X, X)
-FUSE_NMS_OWNER = True   # nms: the owner pass (column argmin) in the chord kernel's epilogue (False: a second read of the matrix)
-# cluster(): the loss reads the shifted points through `center = new_X[indices]` only, so the mean-shift backward runs
-# on those rows alone (MeanShiftRowsFn); 0 = the dense backward of MeanShiftFn + a gather (same numbers; the A/B arm
-# and the path of callers that differentiate through the whole of new_X)
-ROWS_BWD = __import__("os").environ.get("PRIFIT_MS_ROWS", "1") != "0"
-# LABELLED EXPERIMENT, default off: the two products of the mean-shift FORWARD on the 16-bit matrix pipe with
-# error-compensated operands (csrc/meanshift_split.hip): "bf16x3" | "bf16x6" | "fp16x3".  D = 128, N % 256 == 0, and only
-# where the kernel matrix is not kept (the row-sparse backward, i.e. cluster()); anything else takes the fp32 kernels.
-# A number measured with it on is not an fp32 number: bench.py labels it (`dtype`, `experiment`) and never reports it as
-# the headline.
-MS_SPLIT = __import__("os").environ.get("PRIFIT_MS_SPLIT", "0")
-_SPLIT_MODES = {"bf16x3": 1, "bf16x6": 2, "fp16x3": 3}
-split_launches = 0   # updates that took the experiment's kernel (tests assert on it; nothing reads it in the product)
 
 
 def split_mode(N, D, keep_kernel=False):
@@ -71,6 +88,109 @@ def split_mode(N, D, keep_kernel=False):
         return 0
     mode = _SPLIT_MODES[MS_SPLIT]
     return mode if query("prifit_meanshift_split_supported", N, D, mode) else 0
+
+
+def rows_mode(R):
+    return (2 if R <= 32 else 1) if MS_ROWS_MODE == "auto" else int(MS_ROWS_MODE)
+
+
+def rows_supported(N, D, R):
+    return bool(query("prifit_meanshift_rows_supported", N, D, R))
+
+
+class ShiftIter(NamedTuple):
+    """One update of a mean-shift trajectory: the iterate it read, the kernel matrix where it was kept (D = 128: K^T
+    [key][query]; other widths: K), O = K X, rowsum(K), the iterate it wrote and the norms ||O / rowsum|| per row."""
+    Z: torch.Tensor
+    K: Optional[torch.Tensor]
+    O: torch.Tensor
+    rowsum: torch.Tensor
+    Zn: torch.Tensor
+    nrm: torch.Tensor
+
+
+class ShiftRoute(NamedTuple):
+    """The forward arm of the first update and of the others ("split" | "fused" | "gemm"; first may be "chord"), and whether
+    every ShiftIter carries its kernel matrix (the dense backward reads it)."""
+    first: str
+    rest: str
+    kernel_kept: bool
+
+
+class DenseBwdRoute(NamedTuple):
+    """MeanShiftFn.backward: the engine of one iteration ("hybrid" | "fused" | "gemm_kt" | "gemm"), how its two dX terms are
+    formed ("streams" | "dual" | "two" launches; None: the fused engine's own second kernel) and the dZ kernel's schedule."""
+    engine: str
+    dx: Optional[str]
+    balanced: bool
+
+
+class Shifted(NamedTuple):
+    """What _shift hands to nms and _centres: the shifted points (detached) and, on the row-sparse engine, the trajectory
+    (no autograd graph yet) or, on the dense engine, the differentiable Z of MeanShiftFn.  The other field is None."""
+    Z: torch.Tensor
+    traj: Optional[list]
+    Zgrad: Optional[torch.Tensor]
+
+
+class Round(NamedTuple):
+    """One bandwidth -> shift -> nms pass (_round) over the shapes `shapes` ([n] int64 indices into the batch, None: all of
+    it): their X, what the three steps returned, and `accepted` ([n] bool, set by the retry loop's verdict)."""
+    shapes: Optional[torch.Tensor]
+    accepted: Optional[torch.Tensor]
+    X: torch.Tensor
+    bw: torch.Tensor
+    shifted: Shifted
+    ids: torch.Tensor
+    count: torch.Tensor
+    labels: torch.Tensor
+    used: torch.Tensor
+
+
+# The route functions (DESIGN 3.8) launch nothing and allocate nothing: module switches and the library's queries, at every call.
+def _chord_route(same, N, M, D, contiguous, aligned):
+    """chord_matrix: "sym" (a set against itself in whole 128 x 128 tiles, 32-wide k-steps, dense 16-byte-aligned rows: the
+    upper triangle of tiles only, same bits) or "gemm"."""
+    return "sym" if CHORD_SYM and same and N == M and N % 128 == 0 and D % 32 == 0 and contiguous and aligned else "gemm"
+
+
+def _nms_route(N, D, contiguous, aligned):
+    """nms: "mask" (the owner pass in the chord kernel's epilogue, one bit per element, the matrix never written),
+    "float_owner" (the same epilogue, the float matrix read once) or "float" (the matrix read twice)."""
+    if not (FUSE_NMS_OWNER and _chord_route(True, N, N, D, contiguous, aligned) == "sym"):
+        return "float"
+    return "mask" if NMS_MASK else "float_owner"
+
+
+def _forward_route(N, D, keep_kernel, has_chord):
+    """mean_shift_trajectory: D = 128 takes the flash-style kernel (csrc/meanshift_fused.hip) or the MS_SPLIT experiment's,
+    other widths the GEMM chain; the first update reads the caller's chord matrix where nothing else asks for S = X X^T."""
+    rest = "gemm" if D != 128 else "split" if split_mode(N, D, keep_kernel) else "fused"
+    chord = (rest == "fused" and has_chord and not keep_kernel and MS_FIRST_CHORD and
+             query("prifit_meanshift_fused_first_supported", N, D))
+    return ShiftRoute("chord" if chord else rest, rest, bool(keep_kernel))
+
+
+def _dense_bwd_route(N, D):
+    """MeanShiftFn.backward, 4 N^2 D products per iteration in every case but "fused":
+      "hybrid" (default): flash-style dZ kernel (gS = (gO X^T + g_rowsum) * K / b^2 in registers, dZ = gS X, gS^T
+                streamed out once) + ONE dual-source MFMA GEMM for dX += gS^T Z + K^T gO (N % 32 == 0);
+      "gemm_kt" (PRIFIT_MS_BWD=gemm, and every N the kernels above do not take): MFMA GEMM chain on the saved K^T (gS^T by a
+                GEMM epilogue, dZ by a TN GEMM, the same dual-source GEMM or two products): +0.6 ms / step;
+      "fused":  flash-style kernels that re-form gS in registers for dX too (5 products, no gS in HBM; N % 4 == 0): +4.5 ms;
+      "gemm":   the GEMM chain on K, widths other than 128."""
+    if D != 128:
+        return DenseBwdRoute("gemm", "two", False)
+    if BWD_MODE == "fused" and N % 4 == 0:
+        return DenseBwdRoute("fused", None, False)
+    if BWD_MODE == "hybrid" and N % 32 == 0:
+        return DenseBwdRoute("hybrid", "streams" if DX_STREAMS and N % 64 == 0 else "dual", bool(MS_BALANCED))
+    return DenseBwdRoute("gemm_kt", "dual" if N % 32 == 0 else "two", False)
+
+
+def _shift_engine(N, D, slots):
+    """Who differentiates the shift: "rows" (trajectory now, MeanShiftRowsFn on the kept rows later) or "dense" (MeanShiftFn)."""
+    return "rows" if ROWS_BWD and rows_supported(N, D, slots) else "dense"
 
 
 def _bgemm(layout, M, N, K, A, lda, B_, ldb, C, ldc, batch, sA, sB, sC, **kw):
@@ -96,9 +216,7 @@ def chord_matrix(A, B_, owner_key=None):
     Bt, N, D = A.shape
     M = B_.shape[1]
     out = torch.empty(Bt, N, M, dtype=torch.float32, device=A.device)
-    if (CHORD_SYM and A.data_ptr() == B_.data_ptr() and N == M and N % 128 == 0 and D % 32 == 0 and A.is_contiguous() and
-            A.data_ptr() % 16 == 0):
-        # a set against itself: the symmetric kernel computes the upper triangle of tiles only (same bits)
+    if _chord_route(A.data_ptr() == B_.data_ptr(), N, M, D, A.is_contiguous(), A.data_ptr() % 16 == 0) == "sym":
         keys = None
         if owner_key is not None:
             keys = torch.full((Bt, N), -1, dtype=torch.int64, device=A.device)   # all bits set: the atomic-min identity
@@ -110,12 +228,6 @@ def chord_matrix(A, B_, owner_key=None):
         return out
     _bgemm(NT, N, M, D, A, D, B_, D, out, M, Bt, N * D, M * D, N * M, epi=EPI_CHORD)
     return out
-
-
-# The first mean-shift update of a trajectory reads the chord matrix the bandwidth step has just written instead of forming
-# S = X X^T again (csrc/meanshift_fused.hip, SLOAD: Z_0 = X, one of the 20 N x N x D products of ten updates gone).  0: every
-# update takes the standard kernel (A/B arm, tested against this one).
-MS_FIRST_CHORD = __import__("os").environ.get("PRIFIT_MS_FIRST_CHORD", "1") != "0"
 
 
 def compute_bandwidth(X, quantile, num_samples=None, rows=None, keep_chord=None):
@@ -177,76 +289,78 @@ class Normalize2Fn(torch.autograd.Function):
         return gx
 
 
+def _update_split(X, bw, it, Kmat, cut):
+    """The MS_SPLIT experiment's two products, then the fp32 normalisation.  cut: (the dictionary's planes, the mode id)."""
+    global split_launches
+    Bt, N, D = X.shape
+    split_launches += 1
+    with profiler.span("ms_split_fwd[%s]" % MS_SPLIT, 4.0 * Bt * N * N * D):
+        call("prifit_meanshift_split_fwd", ptr(it.Z), ptr(cut[0]), ptr(bw), Bt, N, D, cut[1], ptr(it.O), ptr(it.rowsum), cur_stream())
+    call("prifit_meanshift_update_fwd", ptr(it.O), ptr(it.rowsum), ptr(it.Z), D, _LL(Bt * N), ptr(it.Zn), ptr(it.nrm),
+         cur_stream())
+
+
+def _update_first_chord(X, bw, it, Kmat, chord):
+    """Z_0 = X: S = X X^T = 1 - chord / 2 is in HBM already; ONE matrix product (O = K X) + a read of the chord matrix."""
+    Bt, N, D = X.shape
+    with profiler.span("ms_first_fwd", 2.0 * Bt * N * N * D):
+        call("prifit_meanshift_fused_first_fwd", ptr(X), ptr(chord), _LL(N), _LL(N * N), ptr(bw), Bt, N, D, ptr(it.Zn), ptr(it.O),
+             ptr(it.rowsum), ptr(it.nrm), cur_stream())
+
+
+def _update_fused(X, bw, it, Kmat, _):
+    Bt, N, D = X.shape
+    with profiler.span("ms_fused_fwd", 4.0 * Bt * N * N * D):
+        call("prifit_meanshift_fused_fwd", ptr(it.Z), ptr(X), ptr(bw), Bt, N, D, ptr(Kmat), _LL(N),
+             _LL(N * N), ptr(it.Zn), ptr(it.O), ptr(it.rowsum), ptr(it.nrm), cur_stream())
+
+
+def _update_gemm(X, bw, it, Kmat, _):
+    Bt, N, D = X.shape
+    _bgemm(NT, N, N, D, it.Z, D, X, D, Kmat, N, Bt, N * D, N * D, N * N, epi=EPI_MSKERNEL, epi_scalar=bw)
+    _bgemm(NN, N, D, N, Kmat, N, X, D, it.O, D, Bt, N * N, N * D, N * D, a_rowsum=it.rowsum)  # K X, rowsum(K)
+    call("prifit_meanshift_update_fwd", ptr(it.O), ptr(it.rowsum), ptr(it.Z), D, _LL(Bt * N), ptr(it.Zn), ptr(it.nrm),
+         cur_stream())
+
+
+_UPDATES = {"split": _update_split, "chord": _update_first_chord, "fused": _update_fused, "gemm": _update_gemm}
+
+
 def mean_shift_trajectory(X, bw, iterations, keep_kernel, chord=None):
     """`iterations` updates of src/mean_shift.py:61-82 (gaussian kernel, delta = 1) for all shapes at once, no autograd.
-    X [B,N,D] unit rows (contiguous), bw [B].  Returns (Z_final, per iteration [Z_in, K or None, O, rowsum, Z_out, nrm]);
+    X [B,N,D] unit rows (contiguous), bw [B].  Returns (Z_final, one ShiftIter per iteration);
     keep_kernel=False: the N x N kernel matrix is not kept (D = 128: never written -- prifit_meanshift_fused_fwd with
     KT = NULL; other widths: one scratch matrix for the GEMM chain).
     chord: the chord matrix 2 - 2 X X^T [B,N,N] of THIS X when the caller has it (compute_bandwidth(keep_chord=...)): the
     first update then reads it instead of forming X X^T again (prifit_meanshift_fused_first_fwd; D = 128, N % 64 == 0)."""
-    global split_launches
     Bt, N, D = X.shape
     dev = X.device
-    fused = D == 128  # flash-style kernel (csrc/meanshift_fused.hip); other widths take the GEMM chain
+    route = _forward_route(N, D, keep_kernel, chord is not None)
     # Z_0 = X.clone() (:60): no kernel writes its input iterate, so the first one IS X (a 25 MB copy saved; with no iteration
     # the caller gets its own tensor)
     Z = X if iterations > 0 else X.clone()
     saved = []
     scratch = None
-    split = split_mode(N, D, keep_kernel) if fused else 0
-    if split:   # the dictionary is the same in every iteration (:65): cut once
+    aux = {"chord": chord}
+    if route.rest == "split":   # the dictionary is the same in every iteration (:65): cut once
+        split = _SPLIT_MODES[MS_SPLIT]
         cut = torch.empty(query("prifit_meanshift_split_workspace", Bt, N, D, split), dtype=torch.uint8, device=dev)
         call("prifit_meanshift_split_prep", ptr(X), Bt, N, D, split, ptr(cut), cur_stream())
+        aux["split"] = (cut, split)
     for _ in range(iterations):
         Kmat = None
-        if keep_kernel:
+        if route.kernel_kept:
             Kmat = torch.empty(Bt, N, N, dtype=torch.float32, device=dev)  # fused: K^T [key][query]; else K
-        elif not fused:
+        elif route.rest == "gemm":
             scratch = Kmat = scratch if scratch is not None else torch.empty(Bt, N, N, dtype=torch.float32, device=dev)
-        O = torch.empty(Bt, N, D, dtype=torch.float32, device=dev)
-        rsum = torch.empty(Bt, N, dtype=torch.float32, device=dev)
-        Zn = torch.empty_like(Z)
-        nrm = torch.empty(Bt, N, dtype=torch.float32, device=dev)
-        if split:
-            split_launches += 1
-            with profiler.span("ms_split_fwd[%s]" % MS_SPLIT, 4.0 * Bt * N * N * D):
-                call("prifit_meanshift_split_fwd", ptr(Z), ptr(cut), ptr(bw), Bt, N, D, split, ptr(O), ptr(rsum), cur_stream())
-            call("prifit_meanshift_update_fwd", ptr(O), ptr(rsum), ptr(Z), D, _LL(Bt * N), ptr(Zn), ptr(nrm),
-                 cur_stream())
-        elif (fused and chord is not None and not saved and not keep_kernel and MS_FIRST_CHORD and
-              query("prifit_meanshift_fused_first_supported", N, D)):
-            # Z_0 = X: S = X X^T = 1 - chord / 2 is in HBM already; ONE matrix product (O = K X) + a read of the chord matrix
-            with profiler.span("ms_first_fwd", 2.0 * Bt * N * N * D):
-                call("prifit_meanshift_fused_first_fwd", ptr(X), ptr(chord), _LL(N), _LL(N * N), ptr(bw), Bt, N, D, ptr(Zn), ptr(O),
-                     ptr(rsum), ptr(nrm), cur_stream())
-        elif fused:
-            with profiler.span("ms_fused_fwd", 4.0 * Bt * N * N * D):
-                call("prifit_meanshift_fused_fwd", ptr(Z), ptr(X), ptr(bw), Bt, N, D, ptr(Kmat), _LL(N),
-                     _LL(N * N), ptr(Zn), ptr(O), ptr(rsum), ptr(nrm), cur_stream())
-        else:
-            _bgemm(NT, N, N, D, Z, D, X, D, Kmat, N, Bt, N * D, N * D, N * N, epi=EPI_MSKERNEL, epi_scalar=bw)
-            _bgemm(NN, N, D, N, Kmat, N, X, D, O, D, Bt, N * N, N * D, N * D, a_rowsum=rsum)  # K X, rowsum(K)
-            call("prifit_meanshift_update_fwd", ptr(O), ptr(rsum), ptr(Z), D, _LL(Bt * N), ptr(Zn), ptr(nrm),
-                 cur_stream())
-        saved.append([Z, Kmat if keep_kernel else None, O, rsum, Zn, nrm])
-        Z = Zn
+        it = ShiftIter(Z, Kmat if route.kernel_kept else None, torch.empty(Bt, N, D, dtype=torch.float32, device=dev),
+                       torch.empty(Bt, N, dtype=torch.float32, device=dev), torch.empty_like(Z),
+                       torch.empty(Bt, N, dtype=torch.float32, device=dev))
+        arm = route.rest if saved else route.first
+        _UPDATES[arm](X, bw, it, Kmat, aux.get(arm))
+        saved.append(it)
+        Z = it.Zn
     return Z, saved
-
-
-# How the row-sparse backward runs its T iterations (csrc/meanshift_rows.hip, prifit_meanshift_rows_bwd `mode`):
-#   2  one workgroup per live row runs all T iterations of that row (nothing crosses workgroups): 2 launches;
-#   1  key-tiled iterations as ONE launch over a work queue: 3 launches;  0  one launch per iteration: T + 2 launches.
-# "auto": 2 up to 32 cluster slots per shape (the loss path: ~8 live rows per shape, 148 us against 198 / 221 at B = 24), 1 above
-# (many live rows: the key-tiled forms read the dictionary once for all rows).  profiles/r06_ms_rows.txt.
-MS_ROWS_MODE = os.environ.get("PRIFIT_MS_ROWS_MODE", "auto")
-
-
-def rows_mode(R):
-    return (2 if R <= 32 else 1) if MS_ROWS_MODE == "auto" else int(MS_ROWS_MODE)
-
-
-def rows_supported(N, D, R):
-    return bool(query("prifit_meanshift_rows_supported", N, D, R))
 
 
 class MeanShiftRowsFn(torch.autograd.Function):
@@ -266,10 +380,10 @@ class MeanShiftRowsFn(torch.autograd.Function):
         if not rows_supported(N, D, R):
             raise ValueError("row-sparse mean-shift backward: D in {32, 64, 128}, R <= 32 (got D=%d, R=%d)" % (D, R))
         ids = ids.to(device=X.device, dtype=torch.int64).clamp(0, N - 1).contiguous()
-        Zf = traj[-1][4] if traj else X
+        Zf = traj[-1].Zn if traj else X
         out = torch.gather(Zf, 1, ids.unsqueeze(-1).expand(-1, -1, D))
         # (attributes, not save_for_backward: nothing saved here is an output of this function, so no reference cycle)
-        ctx.traj, ctx.X, ctx.bw, ctx.ids = traj, X, bw, ids
+        ctx.traj, ctx.X, ctx.bw, ctx.ids, ctx.mode = traj, X, bw, ids, rows_mode(R)
         ctx.nrows = None if nrows is None else nrows.to(device=X.device, dtype=torch.int32).contiguous()
         return out
 
@@ -286,11 +400,11 @@ class MeanShiftRowsFn(torch.autograd.Function):
         gX = zero_pool.zeros(Bt, N, D, device=X.device)
         T = len(traj)
         ws = torch.empty(query("prifit_meanshift_rows_bwd_workspace", Bt, N, D, R, T), dtype=torch.float32, device=X.device)
-        arr = lambda k: (ctypes.c_void_p * max(T, 1))(*[it[k].data_ptr() for it in traj])
+        arr = lambda field: (ctypes.c_void_p * max(T, 1))(*[getattr(it, field).data_ptr() for it in traj])
         # HBM-bound: per iteration the dictionary is read once (4 B per element); dX read-modified-written once in all (8 B)
         with profiler.span("ms_rows_bwd", 4.0 * Bt * N * D * (T + 2)):
-            call("prifit_meanshift_rows_bwd", ptr(X), ptr(bw), Bt, N, D, T, arr(0), arr(4), arr(2), arr(3), arr(5), ptr(ids),
-                 ptr(nrows), R, ptr(g), ptr(ws), ptr(gX), rows_mode(R), cur_stream())
+            call("prifit_meanshift_rows_bwd", ptr(X), ptr(bw), Bt, N, D, T, arr("Z"), arr("Zn"), arr("O"), arr("rowsum"), arr("nrm"),
+                 ptr(ids), ptr(nrows), R, ptr(g), ptr(ws), ptr(gX), ctx.mode, cur_stream())
         return gX, None, None, None, None
 
 
@@ -309,89 +423,96 @@ class MeanShiftFn(torch.autograd.Function):
         # save_for_backward (not a python attribute): the last Zn IS the output, and an attribute would close a
         # reference cycle output -> grad_fn -> ctx -> output that only the cyclic GC frees (4 GB of K per step)
         ctx.save_for_backward(X, bw, *[t for it in saved for t in it])
-        ctx.fused = X.shape[2] == 128
+        ctx.route = _dense_bwd_route(X.shape[1], X.shape[2])
         return Z
 
     @staticmethod
     def backward(ctx, g):
         X, bw = ctx.saved_tensors[:2]
         flat = ctx.saved_tensors[2:]
-        saved = [flat[i:i + 6] for i in range(0, len(flat), 6)]
+        n = len(ShiftIter._fields)
+        saved = [ShiftIter(*flat[i:i + n]) for i in range(0, len(flat), n)]
+        route = ctx.route
         Bt, N, D = X.shape
         dev = X.device
         g = g.contiguous()
         gX = zero_pool.zeros(Bt, N, D, device=dev)
-        # Backward engine for the fused (K^T) layout, 4 N^2 D products per iteration in every case but "fused":
-        #   "hybrid" (default): flash-style dZ kernel (gS = (gO X^T + g_rowsum) * K / b^2 in registers, dZ = gS X, gS^T
-        #             streamed out once) + ONE dual-source MFMA GEMM for dX += gS^T Z + K^T gO;
-        #   "gemm":   MFMA GEMM chain (gS^T by a GEMM epilogue, dZ by a TN GEMM, the same dual-source GEMM): +0.6 ms / step;
-        #   "fused":  flash-style kernels that re-form gS in registers for dX too (5 products, no gS in HBM): +4.5 ms.
-        mode = BWD_MODE if (ctx.fused and N % 4 == 0) else "gemm"
-        if mode == "hybrid" and N % 32:
-            mode = "gemm"
-        gS = None if mode == "fused" else torch.empty(Bt, N, N, dtype=torch.float32, device=dev)
+        gS = None if route.engine == "fused" else torch.empty(Bt, N, N, dtype=torch.float32, device=dev)
         gO = torch.empty(Bt, N, D, dtype=torch.float32, device=dev)
         grs = torch.empty(Bt, N, dtype=torch.float32, device=dev)
-        sM, sV = N * N, N * D
-        for Z, Kmat, O, rsum, Zn, nrm in reversed(saved):
-            call("prifit_meanshift_update_bwd", ptr(g), ptr(Zn), ptr(nrm), ptr(O), ptr(rsum), D, Bt, N, ptr(gO),
-                 _LL(sV), ptr(grs), cur_stream())
-            sk = _skinny_splitk(N, D, N, Bt)
-            sk2 = _skinny_splitk(N, D, 2 * N, Bt)
-            balanced = mode == "hybrid" and MS_BALANCED
-            if balanced:
+        sk = _skinny_splitk(N, D, N, Bt)
+        for it in reversed(saved):
+            call("prifit_meanshift_update_bwd", ptr(g), ptr(it.Zn), ptr(it.nrm), ptr(it.O), ptr(it.rowsum), D, Bt, N, ptr(gO),
+                 _LL(N * D), ptr(grs), cur_stream())
+            if route.balanced:
                 gZ = zero_pool.zeros(Bt, N, D, device=dev)   # stream-K schedule: split query blocks add their halves
             else:
-                gZ = (torch.zeros if sk > 1 and mode == "gemm" else torch.empty)(Bt, N, D, dtype=torch.float32, device=dev)
-            if mode == "hybrid":
-                # flash-style dZ kernel (products 1 + 2, streams gS^T out) + both dX terms as one dual-source product
-                with profiler.span("ms_fused_bwd", 4.0 * Bt * N * N * D):
-                    call("prifit_meanshift_fused_bwd_dz", ptr(gO), _LL(sV), ptr(X), ptr(bw), ptr(grs), ptr(Kmat),
-                         _LL(N), _LL(sM), ptr(gS), Bt, N, D, ptr(gZ), int(balanced), cur_stream())
-                if N % 64 == 0 and DX_STREAMS:
-                    with profiler.span("ms_fused_dx", 4.0 * Bt * N * D * N):
-                        call("prifit_meanshift_dx_streams", ptr(gO), ptr(Z), ptr(gS), ptr(Kmat), _LL(N), _LL(sM), Bt, N, D,
-                             ptr(gX), cur_stream())
-                else:
-                    with profiler.span("gemm_dual_nn", 4.0 * Bt * N * D * N):
-                        call("prifit_gemm_dual_nn_f32", N, D, N, N, ptr(gS), ptr(Kmat), _LL(N), _LL(sM), ptr(Z), ptr(gO),
-                             _LL(D), _LL(sV), ptr(gX), _LL(D), _LL(sV), Bt, sk2, 1, cur_stream())
-            elif mode == "fused":
-                with profiler.span("ms_fused_bwd", 10.0 * Bt * N * N * D):
-                    call("prifit_meanshift_fused_bwd_dz", ptr(gO), _LL(sV), ptr(X), ptr(bw), ptr(grs), ptr(Kmat),
-                         _LL(N), _LL(sM), None, Bt, N, D, ptr(gZ), 0, cur_stream())           # dZ  = gS X
-                    call("prifit_meanshift_fused_bwd_dx", ptr(gO), ptr(Z), ptr(X), ptr(bw), ptr(grs), ptr(Kmat),
-                         _LL(N), _LL(sM), Bt, N, D, ptr(gX), cur_stream())                    # dX += gS^T Z + K^T gO
-            elif ctx.fused:
-                # the transposed (key-major) orientation of the saved K^T:
-                # gS^T = (X gO^T + 1 g_rowsum^T) * K^T / b^2 where the clamp is inactive
-                _bgemm(NT, N, N, D, X, D, gO, D, gS, N, Bt, sV, sV, sM, epi=EPI_MSBWD, epi_scalar=bw, aux=Kmat,
-                       ld_aux=N, s_aux=sM, bias=grs, bias_stride=N)
-                _bgemm(TN, N, D, N, gS, N, X, D, gZ, D, Bt, sM, sV, sV, splitk=sk)                       # dZ  = gS X
-                if N % 32 == 0:
-                    # dX += gS^T Z + K^T gO as one product over 2N (one epilogue of float atomics instead of two)
-                    with profiler.span("gemm_nn_bn128", 4.0 * Bt * N * D * N):
-                        call("prifit_gemm_dual_nn_f32", N, D, N, N, ptr(gS), ptr(Kmat), _LL(N), _LL(sM), ptr(Z), ptr(gO),
-                             _LL(D), _LL(sV), ptr(gX), _LL(D), _LL(sV), Bt, sk2, 1, cur_stream())
-                else:
-                    _bgemm(NN, N, D, N, gS, N, Z, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += gS^T Z
-                    _bgemm(NN, N, D, N, Kmat, N, gO, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)   # dX += K^T gO
-            else:
-                # dL/dS = (gO X^T + g_rowsum 1^T) * K / b^2 where the clamp is inactive
-                _bgemm(NT, N, N, D, gO, D, X, D, gS, N, Bt, sV, sV, sM, epi=EPI_MSBWD, epi_scalar=bw, aux=Kmat,
-                       ld_aux=N, s_aux=sM, row_add=grs)
-                _bgemm(NN, N, D, N, gS, N, X, D, gZ, D, Bt, sM, sV, sV, splitk=sk)                       # dZ = dS X
-                _bgemm(TN, N, D, N, gS, N, Z, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += dS^T Z
-                _bgemm(TN, N, D, N, Kmat, N, gO, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)   # dX += K^T dO
+                chain = sk > 1 and route.engine in ("gemm_kt", "gemm")    # split-K products accumulate
+                gZ = (torch.zeros if chain else torch.empty)(Bt, N, D, dtype=torch.float32, device=dev)
+            _DENSE_BWD[route.engine](route, X, bw, it, gO, grs, gS, gZ, gX, sk)
             g = gZ
         gX += g  # Z_0 = X.clone()
         return gX, None, None
 
 
-# nms reads ONE BIT per element of its chord matrix once the owner pass is fused into the kernel that forms it: the matrix is
-# then never written (csrc/gemm.hip chord_sym_kernel MODE 2: 12.6 MB of mask instead of 403 MB at B = 24, N = 2048).  0: the
-# float matrix (A/B arm, tested equal).
-NMS_MASK = os.environ.get("PRIFIT_NMS_MASK", "1") != "0"
+def _dx_dual(span, X, it, gO, gS, gX):
+    """dX += gS^T Z + K^T gO as one product over 2N (one epilogue of float atomics instead of two)."""
+    Bt, N, D = X.shape
+    with profiler.span(span, 4.0 * Bt * N * D * N):
+        call("prifit_gemm_dual_nn_f32", N, D, N, N, ptr(gS), ptr(it.K), _LL(N), _LL(N * N), ptr(it.Z), ptr(gO),
+             _LL(D), _LL(N * D), ptr(gX), _LL(D), _LL(N * D), Bt, _skinny_splitk(N, D, 2 * N, Bt), 1, cur_stream())
+
+
+def _bwd_hybrid(route, X, bw, it, gO, grs, gS, gZ, gX, sk):
+    """Flash-style dZ kernel (products 1 + 2, streams gS^T out) + both dX terms from the two streams."""
+    Bt, N, D = X.shape
+    with profiler.span("ms_fused_bwd", 4.0 * Bt * N * N * D):
+        call("prifit_meanshift_fused_bwd_dz", ptr(gO), _LL(N * D), ptr(X), ptr(bw), ptr(grs), ptr(it.K),
+             _LL(N), _LL(N * N), ptr(gS), Bt, N, D, ptr(gZ), int(route.balanced), cur_stream())
+    if route.dx == "streams":
+        with profiler.span("ms_fused_dx", 4.0 * Bt * N * D * N):
+            call("prifit_meanshift_dx_streams", ptr(gO), ptr(it.Z), ptr(gS), ptr(it.K), _LL(N), _LL(N * N), Bt, N, D,
+                 ptr(gX), cur_stream())
+    else:
+        _dx_dual("gemm_dual_nn", X, it, gO, gS, gX)
+
+
+def _bwd_fused(route, X, bw, it, gO, grs, gS, gZ, gX, sk):
+    Bt, N, D = X.shape
+    with profiler.span("ms_fused_bwd", 10.0 * Bt * N * N * D):
+        call("prifit_meanshift_fused_bwd_dz", ptr(gO), _LL(N * D), ptr(X), ptr(bw), ptr(grs), ptr(it.K),
+             _LL(N), _LL(N * N), None, Bt, N, D, ptr(gZ), 0, cur_stream())           # dZ  = gS X
+        call("prifit_meanshift_fused_bwd_dx", ptr(gO), ptr(it.Z), ptr(X), ptr(bw), ptr(grs), ptr(it.K),
+             _LL(N), _LL(N * N), Bt, N, D, ptr(gX), cur_stream())                    # dX += gS^T Z + K^T gO
+
+
+def _bwd_gemm_kt(route, X, bw, it, gO, grs, gS, gZ, gX, sk):
+    """The transposed (key-major) orientation of the saved K^T: gS^T = (X gO^T + 1 g_rowsum^T) * K^T / b^2 where the clamp is
+    inactive."""
+    Bt, N, D = X.shape
+    sM, sV = N * N, N * D
+    _bgemm(NT, N, N, D, X, D, gO, D, gS, N, Bt, sV, sV, sM, epi=EPI_MSBWD, epi_scalar=bw, aux=it.K,
+           ld_aux=N, s_aux=sM, bias=grs, bias_stride=N)
+    _bgemm(TN, N, D, N, gS, N, X, D, gZ, D, Bt, sM, sV, sV, splitk=sk)                       # dZ  = gS X
+    if route.dx == "dual":
+        _dx_dual("gemm_nn_bn128", X, it, gO, gS, gX)
+    else:
+        _bgemm(NN, N, D, N, gS, N, it.Z, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += gS^T Z
+        _bgemm(NN, N, D, N, it.K, N, gO, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += K^T gO
+
+
+def _bwd_gemm(route, X, bw, it, gO, grs, gS, gZ, gX, sk):
+    """dL/dS = (gO X^T + g_rowsum 1^T) * K / b^2 where the clamp is inactive."""
+    Bt, N, D = X.shape
+    sM, sV = N * N, N * D
+    _bgemm(NT, N, N, D, gO, D, X, D, gS, N, Bt, sV, sV, sM, epi=EPI_MSBWD, epi_scalar=bw, aux=it.K,
+           ld_aux=N, s_aux=sM, row_add=grs)
+    _bgemm(NN, N, D, N, gS, N, X, D, gZ, D, Bt, sM, sV, sV, splitk=sk)                       # dZ = dS X
+    _bgemm(TN, N, D, N, gS, N, it.Z, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += dS^T Z
+    _bgemm(TN, N, D, N, it.K, N, gO, D, gX, D, Bt, sM, sV, sV, accumulate=True, splitk=sk)      # dX += K^T dO
+
+
+_DENSE_BWD = {"hybrid": _bwd_hybrid, "fused": _bwd_fused, "gemm_kt": _bwd_gemm_kt, "gemm": _bwd_gemm}
 
 
 def nms(Z, bw):
@@ -408,7 +529,8 @@ def nms(Z, bw):
     ids = torch.empty(Bt, NMS_CAP, **i32)
     count = torch.empty(Bt, **i32)
     labels = torch.empty(Bt, N, **i32)
-    if (NMS_MASK and FUSE_NMS_OWNER and CHORD_SYM and N % 128 == 0 and D % 32 == 0 and Z.is_contiguous() and Z.data_ptr() % 16 == 0):
+    route = _nms_route(N, D, Z.is_contiguous(), Z.data_ptr() % 16 == 0)
+    if route == "mask":
         okey = torch.full((Bt, N), -1, dtype=torch.int64, device=dev)             # all bits set: the atomic-min identity
         mask = torch.empty(Bt, N, N // 32, **i32)
         nt = N // 128
@@ -418,8 +540,8 @@ def nms(Z, bw):
             call("prifit_nms_mask", ptr(mask), ptr(Z), Bt, N, D, NMS_CAP, ptr(okey), ptr(owner), ptr(counts), ptr(flags), ptr(ids),
                  ptr(count), ptr(labels), ptr(used), cur_stream())
         return ids, count, labels, used
-    keys = [] if FUSE_NMS_OWNER else None
-    dist = chord_matrix(Z, Z, keys)
+    keys = [] if route == "float_owner" else None
+    dist = chord_matrix(Z, Z, keys)      # (float_owner: the symmetric kernel, which leaves the owner keys)
     okey = keys[0] if keys else None
     # the chord matrix is read once (neighbour pick) when the owner pass ran in the chord kernel's epilogue, else twice
     with profiler.span("nms", (4.0 if okey is not None else 8.0) * Bt * N * N):
@@ -729,45 +851,52 @@ def speculative():
 
 
 def _shift(X, bw, iterations, km=KM, chord=None):
-    """The shifted points for nms + what the centre gather needs afterwards: (Z detached, handle).  Row-sparse engine:
-    handle = the trajectory (no autograd graph yet); dense engine: handle = the differentiable Z of MeanShiftFn."""
+    """The shifted points for nms + what the centre gather needs afterwards (Shifted)."""
     Bt, N, D = X.shape
-    if ROWS_BWD and rows_supported(N, D, km):
+    if _shift_engine(N, D, km) == "rows":
         with torch.no_grad():
             Xc = X.detach().contiguous()
             Z, traj = mean_shift_trajectory(Xc, bw, iterations, keep_kernel=False, chord=chord)
-        return Z, traj
+        return Shifted(Z, traj, None)
     Z = MeanShiftFn.apply(X, bw, iterations)
-    return Z.detach(), Z
+    return Shifted(Z.detach(), None, Z)
 
 
-def _centres(X, bw, handle, ids, count):
+def _centres(X, bw, shifted, ids, count):
     """center = new_X[indices] (src/mean_shift.py:46), [B,KM,D], differentiable w.r.t. X."""
-    if isinstance(handle, list):
-        return MeanShiftRowsFn.apply(X, bw, ids, count, handle)      # (the kernels clamp the live count to the KM slots)
-    return torch.gather(handle, 1, ids.unsqueeze(-1).expand(-1, -1, X.shape[2]))
+    if shifted.traj is not None:
+        return MeanShiftRowsFn.apply(X, bw, ids, count, shifted.traj)      # (the kernels clamp the live count to the KM slots)
+    return torch.gather(shifted.Zgrad, 1, ids.unsqueeze(-1).expand(-1, -1, X.shape[2]))
+
+
+def _round(X, q, iterations, km, num_samples, rows, shapes):
+    """compute_bandwidth (which keeps its chord matrix for the first update) -> _shift -> nms on X, the shapes `shapes`
+    of the batch, at quantile q -> Round (not yet judged: `accepted` is None)."""
+    keep = []
+    with torch.no_grad():
+        bw = compute_bandwidth(X, q, num_samples, rows, keep_chord=keep)
+    shifted = _shift(X, bw, iterations, km, chord=keep[0] if keep else None)
+    del keep
+    with torch.no_grad():
+        ids, count, labels, used = nms(shifted.Z, bw)
+    return Round(shapes, None, X, bw, shifted, ids, count, labels, used)
 
 
 def _cluster_speculative(X, quantile, iterations, max_num_clusters, num_samples=None, bandwidth_rows=None):
     Bt, N, D = X.shape
     km = slots_for(max_num_clusters)
-    keep = []
+    rnd = _round(X, quantile, iterations, km, num_samples, bandwidth_rows, None)
     with torch.no_grad():
-        bw = compute_bandwidth(X, quantile, num_samples, bandwidth_rows, keep_chord=keep)
-    Z, handle = _shift(X, bw, iterations, km, chord=keep[0] if keep else None)
-    del keep
-    with torch.no_grad():
-        ids, count, labels, used = nms(Z, bw)
         bad = torch.empty(1, dtype=torch.int32, device=X.device)
-        call("prifit_cluster_verdict", ptr(count), ptr(used), Bt, NMS_CAP, int(max_num_clusters), km, None, ptr(bad),
+        call("prifit_cluster_verdict", ptr(rnd.count), ptr(rnd.used), Bt, NMS_CAP, int(max_num_clusters), km, None, ptr(bad),
              cur_stream())
         flag = _pinned_flag()
         flag.copy_(bad, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         _spec.checks.append((ev, flag))
-    return {"bw": bw, "ids": ids[:, :km].long(), "count": count, "labels": labels.long(),
-            "quantile": [quantile] * Bt, "Z": Z, "_handle": handle}
+    return {"bw": rnd.bw, "ids": rnd.ids[:, :km].long(), "count": rnd.count, "labels": rnd.labels.long(),
+            "quantile": [quantile] * Bt, "Z": rnd.shifted.Z, "_shifted": rnd.shifted}
 
 
 def _pin_representatives(res, center_ids):
@@ -809,7 +938,7 @@ def cluster(X, quantile, iterations, max_num_clusters, center_ids=None, num_samp
         res = _cluster_speculative(X, quantile, iterations, max_num_clusters, num_samples, bandwidth_rows)
         if center_ids is not None:
             _pin_representatives(res, center_ids)
-        res["centres"] = _centres(X, res["bw"], res.pop("_handle"), res["ids"], res["count"])
+        res["centres"] = _centres(X, res["bw"], res.pop("_shifted"), res["ids"], res["count"])
         res["W"] = MembershipFn.apply(res["centres"], X, res["bw"], res["count"])
         return res
     km = slots_for(max_num_clusters)
@@ -818,24 +947,20 @@ def cluster(X, quantile, iterations, max_num_clusters, center_ids=None, num_samp
            "labels": torch.zeros(Bt, N, dtype=torch.int64, device=dev), "quantile": [quantile] * Bt}
     pending = torch.arange(Bt, device=dev)
     q = quantile
-    rounds = []   # (shapes of the round, accepted mask, X of the round, bw, Z detached, handle)
+    rounds = []   # the Rounds that accepted at least one shape
     while pending.numel():
         Xp = X if pending.numel() == Bt else X.index_select(0, pending)
-        with torch.no_grad():
-            rows_p = bandwidth_rows
-            if rows_p is not None and pending.numel() != Bt:
+        rows_p = bandwidth_rows
+        if rows_p is not None and pending.numel() != Bt:
+            with torch.no_grad():
                 rows_p = rows_p.to(dev).index_select(0, pending)
-            keep = []
-            bw = compute_bandwidth(Xp, q, num_samples, rows_p, keep_chord=keep)
-        Z, handle = _shift(Xp, bw, iterations, km, chord=keep[0] if keep else None)
-        del keep
+        rnd = _round(Xp, q, iterations, km, num_samples, rows_p, pending)
         with torch.no_grad():
-            ids, count, labels, used = nms(Z, bw)
-            nb = count.shape[0]
+            nb = rnd.count.shape[0]
             both = torch.empty(2, nb, dtype=torch.int32, device=dev)
-            both[0].copy_(count)
+            both[0].copy_(rnd.count)
             scratch = torch.empty(1, dtype=torch.int32, device=dev)
-            call("prifit_cluster_verdict", ptr(count), ptr(used), nb, NMS_CAP, int(max_num_clusters), km, ptr(both[1]),
+            call("prifit_cluster_verdict", ptr(rnd.count), ptr(rnd.used), nb, NMS_CAP, int(max_num_clusters), km, ptr(both[1]),
                  ptr(scratch), cur_stream())
             host = both.cpu()  # the one host sync of the round (guard_mean_shift's check)
         ok = host[1] <= max_num_clusters
@@ -844,33 +969,33 @@ def cluster(X, quantile, iterations, max_num_clusters, center_ids=None, num_samp
         okd = ok.to(dev)
         sel = pending[okd]
         if sel.numel():
-            res["bw"][sel] = bw[okd]
-            res["ids"][sel] = ids[okd][:, :km].long()
-            res["count"][sel] = count[okd]
-            res["labels"][sel] = labels[okd].long()
-            rounds.append((pending, okd, Xp, bw, Z, handle))
+            res["bw"][sel] = rnd.bw[okd]
+            res["ids"][sel] = rnd.ids[okd][:, :km].long()
+            res["count"][sel] = rnd.count[okd]
+            res["labels"][sel] = rnd.labels[okd].long()
+            rounds.append(rnd._replace(accepted=okd))
             for i in sel.tolist():
                 res["quantile"][i] = q
         pending = pending[~okd]
         q *= 2
-    if len(rounds) == 1 and bool(rounds[0][1].all()):
-        Zfull = rounds[0][4]
+    whole = len(rounds) == 1 and bool(rounds[0].accepted.all())    # one round accepted every shape: its tensors ARE the batch's
+    if whole:
+        res["Z"] = rounds[0].shifted.Z
     else:
-        Zfull = torch.zeros(Bt, N, D, device=dev).index_copy(0, torch.cat([p[o] for p, o, *_ in rounds]),
-                                                             torch.cat([z[o] for _, o, _, _, z, _ in rounds]))
-    res["Z"] = Zfull
+        res["Z"] = torch.zeros(Bt, N, D, device=dev).index_copy(0, torch.cat([r.shapes[r.accepted] for r in rounds]),
+                                                                torch.cat([r.shifted.Z[r.accepted] for r in rounds]))
     if center_ids is not None:
         _pin_representatives(res, center_ids)
     # center = new_X[indices] (:46), per round: a shape's centres come from the trajectory of the round that accepted it
-    if len(rounds) == 1 and bool(rounds[0][1].all()):
-        _, _, Xp, bw, _, handle = rounds[0]
-        centres = _centres(Xp, bw, handle, res["ids"], res["count"])
+    if whole:
+        centres = _centres(rounds[0].X, rounds[0].bw, rounds[0].shifted, res["ids"], res["count"])
     else:
         centres = torch.zeros(Bt, km, D, device=dev)
-        for shapes, okd, Xp, bw, _, handle in rounds:
-            live = torch.where(okd, res["count"].index_select(0, shapes), torch.zeros_like(res["count"].index_select(0, shapes)))
-            cen = _centres(Xp, bw, handle, res["ids"].index_select(0, shapes), live)
-            centres = centres.index_copy(0, shapes[okd], cen[okd])
+        for r in rounds:
+            live = torch.where(r.accepted, res["count"].index_select(0, r.shapes),
+                               torch.zeros_like(res["count"].index_select(0, r.shapes)))
+            cen = _centres(r.X, r.bw, r.shifted, res["ids"].index_select(0, r.shapes), live)
+            centres = centres.index_copy(0, r.shapes[r.accepted], cen[r.accepted])
     res["centres"] = centres
     res["W"] = MembershipFn.apply(centres, X, res["bw"], res["count"])
     return res

@@ -41,25 +41,17 @@ class MeanShift:
             with torch.no_grad():
                 _, indices, labels = self.nms(new_X.detach(), new_X.detach(), b=bw)
             return new_X[indices], bw, labels
-        N, D = X.shape
-        rows = fit_ops.ROWS_BWD and fit_ops.rows_supported(N, D, fit_ops.KM_MAX)
-        if rows:   # the gradient enters through `new_X[indices]` (:46) alone: trajectory now, row-sparse backward later
-            with torch.no_grad():
-                Z, traj = fit_ops.mean_shift_trajectory(Xb.detach(), bwb, iterations, keep_kernel=False)
-        else:
-            Zg = fit_ops.MeanShiftFn.apply(Xb, bwb, iterations)
-            Z = Zg.detach()
+        # (the gradient enters through `new_X[indices]` (:46) alone: fit_ops._shift_engine(N, D, KM_MAX) says who carries it)
+        shifted = fit_ops._shift(Xb, bwb, iterations, fit_ops.KM_MAX)
         with torch.no_grad():
-            ids, count, labels, _ = fit_ops.nms(Z, bwb)
+            ids, count, labels, _ = fit_ops.nms(shifted.Z, bwb)
         K = int(count.item())
         if K > fit_ops.NMS_CAP:
             raise RuntimeError("more than %d clusters" % fit_ops.NMS_CAP)
-        ids = ids[:, :K].long()
-        if rows and K <= fit_ops.KM_MAX:
-            return fit_ops.MeanShiftRowsFn.apply(Xb, bwb, ids, None, traj)[0], bw, labels[0].long()
-        if rows:   # more kept centres than row slots: the dense engine
+        if shifted.traj is not None and K > fit_ops.KM_MAX:   # more kept centres than row slots: the dense engine
             Zg = fit_ops.MeanShiftFn.apply(Xb, bwb, iterations)
-        return Zg[0][ids[0]], bw, labels[0].long()
+            shifted = fit_ops.Shifted(Zg.detach(), None, Zg)
+        return fit_ops._centres(Xb, bwb, shifted, ids[:, :K].long(), None)[0], bw, labels[0].long()
 
     def mean_shift_(self, X, b, iterations=10, kernel_type="gaussian"):
         """upstream :50-84 -> (new_X, X)."""
