@@ -388,7 +388,8 @@ int prifit_gn_param_grads(const double *S, int Bs, int C, float *dgamma, float *
 /* Batch statistics -> affine form of BatchNorm (torch.nn.BatchNorm{1,2}d in train mode, as used at
  * models/pointnet_util.py:198,254,312): mean/var over `count` positions from the partial slabs,
  * scale = gamma*invstd, shift = beta - mean*scale; running stats (may be NULL) updated with
- * `momentum` and the unbiased variance. */
+ * `momentum` and the unbiased variance; count == 1 has no unbiased estimate (torch raises there): the running variance
+ * then takes the biased one, which is 0. */
 int prifit_bn_finalize(const float *slab, int nslab, int C, double count, const float *gamma,
                        const float *beta, float eps, float momentum, float *running_mean,
                        float *running_var, float *scale, float *shift, float *mean, float *invstd,
@@ -416,7 +417,9 @@ int prifit_pool_fwd(const float *Y, long long ldy, const float *scale, const flo
  * following BatchNorm. */
 int prifit_gather_linear_fwd(const float *U, const float *Vc, const float *bias, const int32_t *idx, int B,
                              int N, int S, int K, int C, float *Y, float *slab, void *stream);
-/* autograd: dU [B,N,C] (initialised by the caller) += scatter of dY; dVc [B,S,C] = -sum_k dY. */
+/* autograd: dU [B,N,C] (initialised by the caller) += scatter of dY; dVc [B,S,C] = -sum_k dY.  A row whose index lies outside
+ * [0, N) is the bias alone in the forward (neither U nor Vc enters it), so its dY enters neither dU nor dVc -- in this and in
+ * every other backward form of the layer (_bwd_pool, _bwd_bn, _bwd_csr). */
 int prifit_gather_linear_bwd(const float *dY, const int32_t *idx, int B, int N, int S, int K, int C,
                              float *dU, float *dVc, void *stream);
 /* Backward of a max-pooled, normalised by-linearity layer in one pass (the DGCNN edge convolution of src/dgcnn.py:98-107,

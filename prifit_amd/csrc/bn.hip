@@ -71,6 +71,23 @@ __device__ __forceinline__ void st4g(float *p, float4 v) { *reinterpret_cast<flo
 // f(row, c4, acc0, acc1) accumulates two float4 partials per thread.
 constexpr int POOL_RED_ROWS = 16;  // groups per workgroup in the pooled-layer reduction (only G = P/K rows: keep the grid wide)
 
+__device__ __forceinline__ void add4(float4 &a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+
+// Sum of the `lanes` row-lane partials of column `col` (entries col + l * cols of both halves of s_red) by the column's own
+// thread, pairwise in a fixed tree: partial l absorbs partial l + st for st = 1, 2, 4 ...  One thread adding them one after
+// the other put 128 .. 256 roundings of one sign on top of each other at C <= 12 (a run of equal rows, as a padded ball gives,
+// is exact in the tree), which measured 4 .. 10 x the error of a plain float32 sum (tests/test_gpu_norm_pool_guards.py).
+__device__ __forceinline__ void lane_tree_sum(float4 (*s_red)[256], int col, int cols, int lanes, float4 &t0, float4 &t1)
+{
+    for (int st = 1; st < lanes; st <<= 1)
+        for (int l = 0; l + st < lanes; l += 2 * st) {
+            add4(s_red[0][col + l * cols], s_red[0][col + (l + st) * cols]);
+            add4(s_red[1][col + l * cols], s_red[1][col + (l + st) * cols]);
+        }
+    t0 = s_red[0][col];
+    t1 = s_red[1][col];
+}
+
 template <int ROWS = RED_ROWS, typename F>
 __device__ __forceinline__ void column_reduce(int P, int C, float *__restrict__ slab, F f)
 {
@@ -82,18 +99,22 @@ __device__ __forceinline__ void column_reduce(int P, int C, float *__restrict__ 
         const int lanes = 256 / cols;  // row lanes
         const int c4 = cbase + threadIdx.x % cols, rl = threadIdx.x / cols;
         float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-        if (rl < lanes)
-            for (int r = r_begin + rl; r < r_end; r += lanes) f(r, c4, a0, a1);
+        if (rl < lanes) {
+            // two rows at a time into two pairs of partials: half the length of a thread's chain of additions (128 at C >= 1024,
+            // one row lane), and two rows' loads in flight
+            float4 b0 = a0, b1 = a0;
+            int r = r_begin + rl;
+            for (; r + lanes < r_end; r += 2 * lanes) { f(r, c4, a0, a1); f(r + lanes, c4, b0, b1); }
+            if (r < r_end) f(r, c4, a0, a1);
+            add4(a0, b0);
+            add4(a1, b1);
+        }
         s_red[0][threadIdx.x] = a0;
         s_red[1][threadIdx.x] = a1;
         __syncthreads();
         if (threadIdx.x < cols) {
-            float4 t0 = s_red[0][threadIdx.x], t1 = s_red[1][threadIdx.x];
-            for (int l = 1; l < lanes; ++l) {
-                const float4 u0 = s_red[0][threadIdx.x + l * cols], u1 = s_red[1][threadIdx.x + l * cols];
-                t0.x += u0.x; t0.y += u0.y; t0.z += u0.z; t0.w += u0.w;
-                t1.x += u1.x; t1.y += u1.y; t1.z += u1.z; t1.w += u1.w;
-            }
+            float4 t0, t1;
+            lane_tree_sum(s_red, threadIdx.x, cols, lanes, t0, t1);
             st4g(slab + ((size_t)blockIdx.x * 2 + 0) * C + 4 * c4, t0);
             st4g(slab + ((size_t)blockIdx.x * 2 + 1) * C + 4 * c4, t1);
         }
@@ -469,12 +490,8 @@ __global__ __launch_bounds__(256) void gather_linear_fwd_kernel(const float *__r
         s_red[1][threadIdx.x] = a1;
         __syncthreads();
         if (threadIdx.x < cols) {
-            float4 t0 = s_red[0][threadIdx.x], t1 = s_red[1][threadIdx.x];
-            for (int l = 1; l < lanes; ++l) {
-                const float4 u0 = s_red[0][threadIdx.x + l * cols], u1 = s_red[1][threadIdx.x + l * cols];
-                t0.x += u0.x; t0.y += u0.y; t0.z += u0.z; t0.w += u0.w;
-                t1.x += u1.x; t1.y += u1.y; t1.z += u1.z; t1.w += u1.w;
-            }
+            float4 t0, t1;
+            lane_tree_sum(s_red, threadIdx.x, cols, lanes, t0, t1);
             st4g(slab + ((size_t)blockIdx.x * 2 + 0) * C + c, t0);
             st4g(slab + ((size_t)blockIdx.x * 2 + 1) * C + c, t1);
         }
@@ -483,7 +500,8 @@ __global__ __launch_bounds__(256) void gather_linear_fwd_kernel(const float *__r
 }
 
 // autograd: dU[b, idx, :] += dY (float atomics, one lane per float: 256 B contiguous per wave-instruction);
-// dVc[g, :] = -sum_k dY[(g,k), :]
+// dVc[g, :] = -sum_k dY[(g,k), :] over the rows whose index lies in [0, N): the forward makes any other row the bias alone, so
+// its gradient reaches neither U nor Vc (the same in the _pool and _bn forms below)
 __global__ __launch_bounds__(256) void gather_linear_bwd_kernel(const float *__restrict__ dY,
                                                                 const int32_t *__restrict__ idx, int N, int S, int K,
                                                                 int C, long long total, float *__restrict__ dU,
@@ -506,15 +524,13 @@ __global__ __launch_bounds__(256) void gather_linear_bwd_kernel(const float *__r
             for (int j = 0; j < UNR; ++j) { v[j] = src[(size_t)(k + j) * C]; n[j] = ix[k + j]; }
 #pragma unroll
             for (int j = 0; j < UNR; ++j) {
-                if (n[j] >= 0 && n[j] < N) unsafeAtomicAdd(dst + (size_t)n[j] * C, v[j]);
-                acc += v[j];
+                if (n[j] >= 0 && n[j] < N) { unsafeAtomicAdd(dst + (size_t)n[j] * C, v[j]); acc += v[j]; }
             }
         }
         for (; k < K; ++k) {
             const float v = src[(size_t)k * C];
             const int n = ix[k];
-            if (n >= 0 && n < N) unsafeAtomicAdd(dst + (size_t)n * C, v);
-            acc += v;
+            if (n >= 0 && n < N) { unsafeAtomicAdd(dst + (size_t)n * C, v); acc += v; }
         }
         dVc[id] = -acc;
     }
@@ -575,7 +591,7 @@ __global__ __launch_bounds__(GLB_NTH, 2) void gather_linear_bwd_bn_kernel(
         return (t < T && r < K) ? idx[((size_t)b * S + sidx) * K + r] : -1;
     };
     int n_cur = T > 0 ? load_chunk(0) : -1;
-    float2 acc = {0.f, 0.f}, pacc = {0.f, 0.f};
+    float2 acc = {0.f, 0.f}, pacc = {0.f, 0.f}, accq[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
     int first = 0, pad_seen = 0;
     bool pads_here = false;
     const float *gp = G, *yp = Y;
@@ -587,7 +603,7 @@ __global__ __launch_bounds__(GLB_NTH, 2) void gather_linear_bwd_bn_kernel(
         if (k0 == 0) {
             g = (long long)b * S + s_begin + t / nblk;
             gp = G + (size_t)g * K * C + c; yp = Y + (size_t)g * K * C + c;
-            acc = make_float2(0.f, 0.f); pacc = make_float2(0.f, 0.f);
+            accq[0] = accq[1] = accq[2] = accq[3] = make_float2(0.f, 0.f); pacc = make_float2(0.f, 0.f);
             // Padding: a ball with fewer than K points repeats its FIRST index (models/pointnet_util.py:104-106), on sparse clouds
             // in most of the slots -- all of them rows of one point, i.e. of one wave.  The workgroup that owns that point deals
             // the padded slots round-robin over its waves instead; their sum stays in registers and goes to dU with one
@@ -635,13 +651,17 @@ __global__ __launch_bounds__(GLB_NTH, 2) void gather_linear_bwd_bn_kernel(
                             v.x += dx; v.y += dyy;
                             *dst = v;
                         }
-                        acc.x += dx; acc.y += dyy;
+                        accq[j & 3].x += dx; accq[j & 3].y += dyy;
                     }
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
         if (k0 + 64 >= K && GLB_PROBE != 1) {      // the centre's last chunk: its sums leave
+            // (four interleaved chains: the ~K / 4 equal rows a wave gets of a padded ball rounded one way in a single chain,
+            // 4.7 x the error of a plain float32 sum at K = 200)
+            acc.x = (accq[0].x + accq[1].x) + (accq[2].x + accq[3].x);
+            acc.y = (accq[0].y + accq[1].y) + (accq[2].y + accq[3].y);
             if (cok && (acc.x != 0.f || acc.y != 0.f)) {
                 unsafeAtomicAdd(dVc + (size_t)g * C + c, -acc.x);
                 unsafeAtomicAdd(dVc + (size_t)g * C + c + 1, -acc.y);
@@ -880,28 +900,38 @@ __global__ __launch_bounds__(256) void gather_linear_bwd_pool_kernel(
         const float *src = Y + (size_t)g * K * C + c;
         const int32_t *ix = idx + (size_t)g * K;
         float *dst = dU + (size_t)b * N * C + c;
-        float acc = 0.f;
-        int k = 0;
-        for (; k + UNR <= K; k += UNR) {
+        // dVc: 2 UNR interleaved chains, 1 / (2 UNR) of the K roundings each (the rows of a padded ball are equal: in one chain
+        // their roundings all go one way)
+        float acc = 0.f, accs[UNR], accs2[UNR];
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) accs[j] = accs2[j] = 0.f;
+        auto block = [&](int k0, float (&ac)[UNR]) {
             float y[UNR];
             int n[UNR];
 #pragma unroll
-            for (int j = 0; j < UNR; ++j) { y[j] = src[(size_t)(k + j) * C]; n[j] = ix[k + j]; }
+            for (int j = 0; j < UNR; ++j) { y[j] = src[(size_t)(k0 + j) * C]; n[j] = ix[k0 + j]; }
 #pragma unroll
             for (int j = 0; j < UNR; ++j) {
-                const float v = fmaf(a, (k + j) == w ? (fmaf(y[j], s, t) > 0.f ? gv : gv * slope) : 0.f, fmaf(bb, y[j], d));
-                if (n[j] >= 0 && n[j] < N) unsafeAtomicAdd(dst + (size_t)n[j] * C, v);
-                acc += v;
+                const float v = fmaf(a, (k0 + j) == w ? (fmaf(y[j], s, t) > 0.f ? gv : gv * slope) : 0.f, fmaf(bb, y[j], d));
+                if (n[j] >= 0 && n[j] < N) { unsafeAtomicAdd(dst + (size_t)n[j] * C, v); ac[j] += v; }
             }
-        }
+        };
+        int k = 0;
+        for (; k + 2 * UNR <= K; k += 2 * UNR) { block(k, accs); block(k + UNR, accs2); }
+        for (; k + UNR <= K; k += UNR) block(k, accs);
         for (; k < K; ++k) {
             const float y = src[(size_t)k * C];
             const int n = ix[k];
             const float v = fmaf(a, k == w ? (fmaf(y, s, t) > 0.f ? gv : gv * slope) : 0.f, fmaf(bb, y, d));
-            if (n >= 0 && n < N) unsafeAtomicAdd(dst + (size_t)n * C, v);
-            acc += v;
+            if (n >= 0 && n < N) { unsafeAtomicAdd(dst + (size_t)n * C, v); acc += v; }
         }
-        dVc[id] = -acc;
+#pragma unroll
+        for (int j = 0; j < UNR; ++j) accs[j] += accs2[j];
+#pragma unroll
+        for (int st = 1; st < UNR; st <<= 1)
+#pragma unroll
+            for (int j = 0; j + st < UNR; j += 2 * st) accs[j] += accs[j + st];
+        dVc[id] = -(accs[0] + acc);
     }
 }
 

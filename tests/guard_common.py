@@ -80,6 +80,18 @@ def padded_stream(B, N, ld, stride, poison=float("nan"), device="cuda", lead=Non
     return stream, base
 
 
+def guarded_matrix(P, C, ld, lead, tail, poison=float("nan"), device="cuda"):
+    """-> (view, base): a [P, C] float32 view with row stride `ld` >= C inside `base`, for the channels-last matrices the
+    kernels address with a leading dimension (any P, unlike padded_stream).  The pad columns C .. ld - 1 of every row (the last
+    row's too), the guards of at least `lead` floats in front and `tail` behind, and the view itself until the caller fills
+    it, hold poison."""
+    assert ld >= C > 0 and P > 0
+    base = _poisoned(lead + P * ld + tail + 2 * ALIGN // 4, poison, device)
+    s = _start(base, lead)
+    view = base.as_strided((P, C), (ld, 1), base.storage_offset() + s)
+    return view, base
+
+
 def _outside(base, view):
     """bool [base.numel()]: True on the words of `base` that `view` does not cover."""
     off = view.storage_offset() - base.storage_offset()

@@ -1,0 +1,891 @@
+"""The normalisation / activation / max-pool / column-sum kernels of csrc/bn.hip and the by-linearity first layer with its four
+backward forms (csrc/bn.hip, csrc/sa_gather_bwd.hip) through the C ABI at edge shapes, every tensor a kernel reads inside NaN
+guard bands (pad columns of matrices with ld > C included), every tensor it writes inside sentinel guards
+(tests/guard_common.py), against the float64 restatements of tests/bn_common.py.
+
+Each kernel is fed the float64 reference's upstream results rounded to float32 and compared with the reference recomputed from
+those same float32 values, so an error belongs to one kernel; test_whole_layer_* chain the kernels' own outputs against the
+torch-anchored float64 chain (tests/test_bn_restatement.py).  Each case asserts, in this order: outputs finite, guards
+intact, exact properties (first-maximum arg with tie rows, arg = 0 under a zero scale, untouched pad columns and running
+statistics, zero dU rows of points never indexed, bit-equal reruns of the atomics-free kernels), then the bars: error against
+float64 at most 4 x the error of the float32 restatement on the same inputs (floored at 2^-24), element-wise outputs
+normalised by max |fp64|, reduced outputs element by element by the float64 sum of |terms|.
+
+Measured on an MI355X (per quantity the case with the largest ratio: kernel error, float32 restatement's error, their ratio
+with the restatement's error floored at 2^-24, the case; the bar is a ratio of 4; the layer_* rows are the chained tests):
+
+  quantity           kernel   fp32     ratio   case
+  stats_slab         3.9e-07  1.5e-07   2.56   (128, 1028, 0, 0.0)
+  bwd_slab           1.8e-07  8.0e-08   2.24   (128, 1024, 0, 0.2)
+  pool_bwd_slab      8.7e-08  6.4e-08   1.36   (32, 16, 4, 256, 0.2)
+  bnf_scale          7.5e-08  7.5e-08   1.00   (1, 4)
+  bnf_shift          6.0e-08  6.0e-08   1.00   (1, 4)
+  bnf_mean           3.8e-08  6.5e-08   0.59   (256, 1)
+  bnf_invstd         4.2e-08  4.2e-08   0.70   (1, 4)
+  bnf_rmean          8.9e-08  8.9e-08   1.00   (1, 4)
+  bnf_rvar           7.4e-08  2.3e-08   1.24   (256, 4)
+  bnb_dgamma         4.7e-08  8.1e-08   0.59   (3, 100, 1)
+  bnb_dbeta          5.9e-08  7.4e-08   0.79   (3, 100, 1)
+  bnb_b              3.9e-08  3.9e-08   0.66   (3, 100, 1)
+  bnb_d              4.8e-08  8.7e-08   0.55   (3, 100, 1)
+  bnf_mean_cancel    3.7e-08  3.7e-08   0.61   (256, 100)
+  bnf_rmean_cancel   9.3e-08  1.5e-09   1.56   (3, 4)
+  bnf_rvar_cancel    6.2e-08  2.2e-06   0.03   (257, 4)
+  gnf_scale          9.4e-08  9.4e-08   1.00   (256, 1, 1, 1)
+  gnf_shift          6.4e-08  6.1e-08   1.05   (64, 2, 9, 5)
+  gnf_mean           4.1e-08  4.1e-08   0.69   (12, 3, 1, 1)
+  gnf_invstd         4.2e-08  6.0e-08   0.70   (1024, 4, 3, 5)
+  gnf_chsum          0.0e+00  0.0e+00   0.00   (4, 4, 1, 1)
+  gnfo_scale         6.0e-08  6.0e-08   1.00   (256, 1, 1, 1)
+  gnfo_shift         7.7e-08  6.4e-08   1.21   (1024, 4, 9, 1)
+  gnfo_mean          4.9e-08  5.5e-08   0.82   (64, 2, 9, 1)
+  gnfo_invstd        4.1e-08  4.8e-08   0.69   (1024, 4, 9, 1)
+  gnfo_chsum         0.0e+00  0.0e+00   0.00   (4, 4, 1, 1)
+  gnb_cb             4.9e-08  4.9e-08   0.82   (256, 1, 9, 1, 0)
+  gnb_cd             4.8e-08  7.0e-08   0.69   (4, 4, 1, 5, 0)
+  gnb_S              0.0e+00  0.0e+00   0.00   (4, 4, 1, 1, 0)
+  gnp_dgamma         6.0e-08  6.0e-08   1.00   (256, 1, 3, 1, 0)
+  gnp_dbeta          6.0e-08  6.0e-08   1.00   (1024, 4, 3, 1, 0)
+  gnb_dsum           5.2e-08  5.2e-08   0.88   (12, 3, 9, 1, 1)
+  gnp_db             4.0e-08  4.3e-08   0.68   (12, 3, 3, 5, 1)
+  affine             5.2e-08  5.9e-08   0.87   (5, 1028, 1, 0.2)
+  apply_dY           1.0e-07  2.9e-08   1.72   (1, 4, 0, 0.0)
+  pool_out           5.3e-08  5.3e-08   0.88   (40, 8, 4, 32, 0.0)
+  pool_dY            5.5e-08  5.5e-08   0.92   (3, 9, 64, 36, 0.2)
+  pool_table         5.3e-08  5.3e-08   0.89   (1, 1, 4, 0, 0.0)
+  col_sum            1.9e-07  6.3e-08   2.98   (513, 1028)
+  col_sum_smp        2.0e-07  6.4e-08   3.06   (1536, 1028, 512)
+  gl_Y               7.4e-08  7.4e-08   1.00   (5, 1, 1, 132, 1, 0)
+  gl_slab            4.7e-07  3.1e-07   1.51   (130, 17, 65, 132, 1, 1)
+  glb_dU             2.0e-07  1.4e-07   1.40   (300, 33, 200, 12, 0, 1)
+  glb_dVc            2.1e-07  5.0e-08   3.48   (300, 33, 200, 132, 1, 1)
+  glp_dU             1.1e-06  8.3e-07   1.28   (130, 17, 65, 132, 1, 1)
+  glp_dVc            3.6e-07  2.2e-07   1.66   (300, 33, 200, 12, 1, 1)
+  glbn_dU            2.0e-06  2.0e-06   1.00   (300, 33, 200, 6, 1, 1)
+  glbn_dVc           4.2e-07  1.9e-07   2.19   (300, 33, 200, 4, 0, 1)
+  glcsr_dU           1.1e-06  1.1e-06   1.00   (130, 9, 3, 126, 1, 0)
+  glcsr_dVc          2.9e-07  1.6e-07   1.82   (300, 33, 200, 4, 1, 1)
+  layer_scale        5.7e-08  6.7e-08   0.85   bn_leaky
+  layer_shift        8.5e-08  7.8e-08   1.09   gn_offset
+  layer_mean         6.9e-08  3.1e-08   1.15   bn_leaky
+  layer_invstd       5.2e-08  7.0e-08   0.75   bn_leaky
+  layer_rmean        5.2e-08  5.2e-08   0.87   bn_pool_leaky
+  layer_rvar         8.1e-08  8.1e-08   1.00   bn
+  layer_out          1.0e-07  1.3e-07   0.79   bn_leaky
+  layer_dY           8.5e-08  1.0e-07   0.83   bn_pool_leaky
+  layer_dgamma       7.2e-08  7.2e-08   1.00   bn_pool_leaky
+  layer_dbeta        5.9e-08  6.4e-08   0.92   bn_pool_leaky
+  layer_dsum         3.6e-08  5.5e-08   0.61   gn_offset
+  layer_db           2.5e-08  3.9e-08   0.43   gn
+
+The cancellation column (mean 100, spread 1e-2) of prifit_bn_finalize, where float32 is no yardstick: relative error against
+the exact (rational) reference, and the bound that double-precision accumulation allows (worst case):
+
+  quantity           error    bound     case
+  bnf_invstd_cancel  4.0e-08  4.6e-07   (1, 100)
+  bnf_scale_cancel   6.4e-08  4.8e-07   (1, 4)
+  bnf_shift_cancel   7.5e-08  4.8e-07   (1, 4)
+
+Largest difference between two runs of the outputs that are not asserted to repeat, in the unit of the bars (dU and the _bn
+form's dVc are added with float atomics in arrival order; the _csr form's dU sums a CSR list, whose order is not fixed, in
+float64).  A non-zero figure is a finding that is NOT fixed here -- it stays well inside the bar, but the issue asks for an
+order that repeats:
+
+  quantity           largest   case
+  glb_dU             2.1e-07   (300, 33, 200, 132, 1, 0)
+  glp_dU             6.6e-07   (300, 33, 200, 132, 1, 0)
+  glbn_dU            2.1e-07   (130, 17, 65, 126, 1, 0)
+  glbn_dVc           2.4e-07   (300, 33, 200, 128, 1, 1)
+  glcsr_dU           0.0e+00   (5, 1, 1, 4, 1, 0)
+
+Defects these tests found:
+- prifit_gather_linear_bwd and _bwd_pool put the gradient of rows whose index lies outside [0, N) into dVc, although the
+  forward makes such a row the bias alone (the _bn and _csr forms left them out): `acc += v` stood outside the range check.
+  Now every out_of_range case agrees with autograd of the forward restatement in all four forms, at the ratios above.
+- One thread added the row-lane partials of a column one after the other (column_reduce, gather_linear_fwd_kernel), and a
+  thread's own rows in one chain.  Before: stats_slab 2.8e-07 against 6.8e-08 (ratio 4.1) at (300, 4), 6.8e-07 against 1.7e-07
+  at (300, 1028), bwd_slab 2.5e-07 against 3.3e-08 (7.5) at (127, 12), gl_slab 1.6e-06 .. 4.2e-06 against 2.0e-07 .. 8.1e-07
+  (ratios 5 .. 11) at C = 4 -- a padded ball is a run of equal rows, whose roundings all go one way in a chain and vanish in
+  a tree.  Now a pairwise tree over the lanes and two chains per thread: the ratios above.
+- dVc of the _bwd_pool, _bwd_bn and _bwd_csr forms was one chain of K additions per channel.  Before: glp_dVc 8.9e-07 ..
+  3.0e-06 against 2.0e-07 .. 3.9e-07 (ratios 4.1 .. 8.4), glcsr_dVc 9.0e-07 .. 2.7e-06 (4.3 .. 11.5) at K = 64, 65, 200, glbn_dVc
+  1.6e-06 against 3.5e-07 (4.7) at (300, 33, 200, 6); with four chains glp_dVc still reached 1.4e-06 against 3.0e-07 (4.7)
+  at (300, 33, 200, 12).  Now 8 / 4 / 8 interleaved chains: the ratios above.
+Nothing else was found: no guard word was touched, every arg is the first maximum, and every kernel that is asserted to
+repeat its bits does.
+
+What these tests cannot see.  NaN guards show a stray read only if the value read reaches a result.  The tail of
+pool_fwd_kernel's 8-row unroll loads rows k >= K (clamped to K - 1) and drops them at `if (k >= K) break`: with the clamp
+changed to K the kernel reads the next group's first row, or the guard behind Y, and every test here still passes (run once:
+63 passed).  An over-read whose value is discarded is outside what value guards detect, so "no poison was read" holds only for
+reads that are used.  The other mutation -- column_reduce's tail bound `r < r_end` read as `r <= r_end` -- fails all ten
+test_col_stats_and_bwd_reduce / test_pool_bwd_reduce cases with a non-finite slab (run once).
+"""
+import ctypes
+from fractions import Fraction
+
+import pytest
+import torch
+
+import bn_common as bc
+from bn_common import F32, F64
+from guard_common import SENTINEL, assert_guards_intact, guarded, guarded_matrix
+
+pytestmark = pytest.mark.gpu
+
+NAN = float("nan")
+LL = ctypes.c_longlong
+LEAD = 4096
+TAIL = 129 * 1056       # 129 rows of the widest leading dimension any case uses (1028 + 28)
+
+
+@pytest.fixture(scope="module")
+def A(hiplib):
+    assert torch.cuda.is_available()
+    from prifit_amd import _lib
+    return _lib
+
+
+class Bufs:
+    """Guarded buffers of one case: *in = inputs in NaN guards, *out = outputs in SENTINEL guards."""
+
+    def __init__(self):
+        self.items = []
+
+    def _mat(self, P, C, ld, poison):
+        v, base = guarded_matrix(P, C, ld, LEAD, TAIL, poison)
+        self.items.append((base, v, poison))
+        return v
+
+    def fin(self, t, ld=None):
+        t = t.detach().to(F32)
+        if ld is None:
+            v, base = guarded(tuple(t.shape), LEAD, TAIL, NAN)
+            self.items.append((base, v, NAN))
+        else:
+            v = self._mat(t.shape[0], t.shape[1], ld, NAN)
+        v.copy_(t)
+        return v
+
+    def iin(self, t, poison):
+        """int32 input; `poison` is an IN-RANGE value whose use shows in the results (a NaN's bit pattern read as an index is
+        out of range everywhere, and the kernels drop such an index silently)"""
+        v, base = guarded(tuple(t.shape), LEAD, TAIL, int(poison))
+        v.view(torch.int32).copy_(t.to(torch.int32))
+        self.items.append((base, v, int(poison)))
+        return v.view(torch.int32)
+
+    def din(self, t):
+        v, base = guarded(tuple(t.shape[:-1]) + (2 * t.shape[-1],), LEAD, TAIL, NAN)
+        v.view(F64).copy_(t.to(F64))
+        self.items.append((base, v, NAN))
+        return v.view(F64)
+
+    def fout(self, shape, zero=False, init=None):
+        v, base = guarded(tuple(shape), LEAD, TAIL, SENTINEL)
+        if zero:
+            v.zero_()
+        if init is not None:
+            v.copy_(init)
+        self.items.append((base, v, SENTINEL))
+        return v
+
+    def mout(self, P, C, ld, col0=0, wide=None):
+        """[P, C] output at column col0 of a [P, wide] matrix with row stride ld: the other columns are guards too"""
+        m, base = guarded_matrix(P, wide or C, ld, LEAD, TAIL, SENTINEL)
+        v = m[:, col0:col0 + C]
+        self.items.append((base, v, SENTINEL))
+        return v
+
+    def iout(self, shape):
+        return self.fout(shape).view(torch.int32)
+
+    def dout(self, shape):
+        return self.fout(tuple(shape[:-1]) + (2 * shape[-1],)).view(F64)
+
+    def intact(self):
+        torch.cuda.synchronize()
+        for base, v, poison in self.items:
+            assert_guards_intact(base, v, poison)
+
+
+def finite(*ts):
+    torch.cuda.synchronize()
+    for t in ts:
+        assert bool(torch.isfinite(t).all()), "non-finite output"
+
+
+def ld_of(C, i):
+    """A different leading dimension for the i-th operand of a call"""
+    return C + 4 * (i + 1)
+
+
+def tabs_in(g, t, names):
+    return [g.fin(t[n]) for n in names]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# column statistics and the backward partials
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", sorted({c[1] for c in bc.REDUCE_CASES}))
+def test_col_stats_and_bwd_reduce_in_guards_against_fp64(A, C):
+    rep = bc.Report()
+    for P, _, rps, slope in [c for c in bc.REDUCE_CASES if c[1] == C]:
+        case = bc.element_case(P, C, rps, slope)
+        tag = (P, C, rps, slope)
+        nslab = -(-P // bc.RED_ROWS)
+        g = Bufs()
+        same = P % 2 == 0                                   # some cases with ld == C
+        Y = g.fin(case["Y"], C if same else ld_of(C, 0))
+        Gr = g.fin(case["G"], C if same else ld_of(C, 1))
+        sc, sh, mu, isd = tabs_in(g, case, ("scale", "shift", "mean", "invstd"))
+        slab, slab2 = g.fout((nslab, 2, C)), g.fout((nslab, 2, C))
+        for s in (slab, slab2):
+            A.call("prifit_col_stats", A.ptr(Y), LL(Y.stride(0)), P, C, A.ptr(s), A.cur_stream())
+        bslab, bslab2 = g.fout((nslab, 2, C)), g.fout((nslab, 2, C))
+        for s in (bslab, bslab2):
+            A.call("prifit_bn_relu_bwd_reduce", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh),
+                   A.ptr(mu), A.ptr(isd), P, C, rps, slope, A.ptr(s), A.cur_stream())
+        finite(slab, bslab)
+        g.intact()
+        assert torch.equal(slab, slab2) and torch.equal(bslab, bslab2)
+        y64 = case["Y"].to(F64)
+        rep.red("stats_slab", tag, slab, bc.col_stats(case["Y"]), bc.col_stats(case["Y"], dtype=F32),
+                bc.slab_sums(y64.abs(), y64 * y64, bc.RED_ROWS))
+        ref = {}
+        for dt in (F64, F32):
+            Gm = bc.masked_grad(case["G"], case["Y"], case["scale"], case["shift"], rps, slope, dt)
+            t0, t1 = bc.bwd_terms(Gm, case["Y"], case["mean"], case["invstd"], rps, dt)
+            ref[dt] = (t0, t1)
+        rep.red("bwd_slab", tag, bslab, bc.slab_sums(*ref[F64], bc.RED_ROWS), bc.slab_sums(*ref[F32], bc.RED_ROWS, F32),
+                bc.slab_sums(ref[F64][0].abs(), ref[F64][1].abs(), bc.RED_ROWS))
+        rep.assert_bars()
+
+
+@pytest.mark.parametrize("C", sorted({c[2] for c in bc.POOL_REDUCE_CASES}))
+def test_pool_bwd_reduce_in_guards_against_fp64(A, C):
+    rep = bc.Report()
+    for G, K, _, per_sample, slope in [c for c in bc.POOL_REDUCE_CASES if c[2] == C]:
+        rps = 16 * K if per_sample else 0
+        case = bc.pool_case(G, K, C, rps, slope, seed=5)
+        tag = (G, K, C, rps, slope)
+        _, arg = bc.pool_fwd(case["Y"], case["scale"], case["shift"], G, K, rps, slope)
+        nslab = -(-G // bc.POOL_RED_ROWS)
+        g = Bufs()
+        Y, gp = g.fin(case["Y"], ld_of(C, 0)), g.fin(case["gp"], ld_of(C, 1))
+        ai = g.iin(arg, 0)              # guards: winner 0, whose gp row in the guard is NaN
+        sc, sh, mu, isd = tabs_in(g, case, ("scale", "shift", "mean", "invstd"))
+        slab, slab2 = g.fout((nslab, 2, C)), g.fout((nslab, 2, C))
+        for s in (slab, slab2):
+            A.call("prifit_pool_bwd_reduce", A.ptr(gp), LL(gp.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(ai), A.ptr(sc),
+                   A.ptr(sh), A.ptr(mu), A.ptr(isd), G, K, C, rps, slope, A.ptr(s), A.cur_stream())
+        finite(slab)
+        g.intact()
+        assert torch.equal(slab, slab2)
+        ref = {}
+        for dt in (F64, F32):
+            Gm = bc.pooled_grad(case["gp"], case["Y"], arg, case["scale"], case["shift"], G, K, rps, slope, dt)
+            ref[dt] = bc.bwd_terms(Gm, case["Y"], case["mean"], case["invstd"], rps, dt)
+        rows = bc.POOL_RED_ROWS * K
+        rep.red("pool_bwd_slab", tag, slab, bc.slab_sums(*ref[F64], rows), bc.slab_sums(*ref[F32], rows, F32),
+                bc.slab_sums(ref[F64][0].abs(), ref[F64][1].abs(), rows))
+        rep.assert_bars()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# finalize kernels
+# ---------------------------------------------------------------------------------------------------------------------------
+def stat_slabs(n, C, gen, rows=bc.RED_ROWS):
+    """[n][2][C] float32 partial (sum, sum of squares) slabs of `rows` rows each with a positive variance"""
+    mu, sig = torch.randn(C, generator=gen), 0.5 + torch.rand(C, generator=gen)
+    s = rows * mu + (rows ** 0.5) * sig * torch.randn(n, C, generator=gen)
+    q = s * s / rows + rows * sig * sig * (0.8 + 0.4 * torch.rand(n, C, generator=gen))
+    return torch.stack([s, q], 1).to(F32)
+
+
+CONST_COL, CANCEL_COL = 1, 2
+
+
+@pytest.mark.parametrize("nslab,C", bc.FINALIZE_CASES + [(1, 8)])
+def test_bn_finalize_and_bwd_finalize_in_guards_against_fp64(A, nslab, C):
+    rep = bc.Report()
+    gen = bc.gen_of(bc.seed_of(6, nslab, C))
+    one = (nslab, C) == (1, 8)                               # count == 1: a single row
+    count = 1.0 if one else float(nslab * bc.RED_ROWS)
+    slab = stat_slabs(nslab, C, gen)
+    if one:
+        y = torch.randn(C, generator=gen).to(F32)
+        slab = torch.stack([y, y * y]).unsqueeze(0)
+    special = C >= 4 and not one
+    if special:
+        slab[:, 0, CONST_COL], slab[:, 1, CONST_COL] = 1.5 * bc.RED_ROWS, 2.25 * bc.RED_ROWS      # a constant column, exact
+        dev = 1e-2 * torch.randn(nslab, bc.RED_ROWS, generator=gen, dtype=F64) + 100.0                # mean 100, spread 1e-2
+        slab[:, 0, CANCEL_COL], slab[:, 1, CANCEL_COL] = dev.sum(1).to(F32), (dev * dev).sum(1).to(F32)
+    keep = torch.ones(C, dtype=torch.bool)
+    if special:
+        keep[CANCEL_COL] = False
+    gamma, beta = bc.signed(C, 0.5, 1.5, gen), bc.signed(C, 0.1, 1.0, gen)
+    rm0, rv0 = (0.1 * torch.randn(C, generator=gen)).to(F32), (0.5 + torch.rand(C, generator=gen)).to(F32)
+    eps, mom = 1e-5, 0.1
+    g = Bufs()
+    sl, ga, be = g.fin(slab), g.fin(gamma), g.fin(beta)
+    outs = [g.fout((C,)) for _ in range(4)]
+    rm, rv = g.fout((C,), init=rm0), g.fout((C,), init=rv0)
+    A.call("prifit_bn_finalize", A.ptr(sl), nslab, C, count, A.ptr(ga), A.ptr(be), eps, mom, A.ptr(rm), A.ptr(rv),
+           A.ptr(outs[0]), A.ptr(outs[1]), A.ptr(outs[2]), A.ptr(outs[3]), A.cur_stream())
+    finite(rm, rv, *outs)
+    g.intact()
+    rm1, rv1 = rm.clone(), rv.clone()
+    outs2 = [g.fout((C,)) for _ in range(4)]
+    A.call("prifit_bn_finalize", A.ptr(sl), nslab, C, count, A.ptr(ga), A.ptr(be), eps, mom, None, None,
+           A.ptr(outs2[0]), A.ptr(outs2[1]), A.ptr(outs2[2]), A.ptr(outs2[3]), A.cur_stream())
+    finite(*outs2)
+    g.intact()
+    assert torch.equal(rm, rm1) and torch.equal(rv, rv1)                 # running statistics untouched when not passed
+    assert all(torch.equal(a, b) for a, b in zip(outs, outs2))
+    f32eps = float(torch.tensor(eps, dtype=F32))
+    if special:                                                          # the variance clamps to 0: invstd = 1 / sqrt(eps)
+        want = torch.tensor(1.0 / (f32eps ** 0.5), dtype=F64).to(F32)
+        assert float(outs[3][CONST_COL]) == float(want)
+        assert float(outs[2][CONST_COL]) == 1.5
+        assert float(rv[CONST_COL]) == float((torch.tensor(1.0, dtype=F32) - torch.tensor(mom, dtype=F32)) * rv0[CONST_COL])
+    s64, q64 = slab.to(F64)[:, 0].sum(0), slab.to(F64)[:, 1].sum(0)
+    r64 = bc.bn_finalize(s64, q64, count, gamma, beta, f32eps, float(torch.tensor(mom, dtype=F32)), rm0, rv0)
+    r32 = bc.bn_finalize(slab[:, 0].sum(0), slab[:, 1].sum(0), count, gamma, beta, f32eps, mom, rm0, rv0, F32)
+    tag = (nslab, C)
+    got = dict(scale=outs[0], shift=outs[1], mean=outs[2], invstd=outs[3], rmean=rm, rvar=rv)
+    for k in ("scale", "shift", "mean", "invstd", "rmean", "rvar"):
+        rep.ew("bnf_" + k, tag, got[k].cpu()[keep], r64[k][keep], r32[k][keep])
+        if special and k in ("mean", "rmean", "rvar"):
+            c = slice(CANCEL_COL, CANCEL_COL + 1)
+            rep.ew("bnf_" + k + "_cancel", tag, got[k].cpu()[c], r64[k][c], r32[k][c])
+    if special:
+        # The cancellation column: float32 cannot form q / n - mean^2 there (its error is of order 1), so it is no yardstick.
+        # The reference is EXACT (rational arithmetic on the float32 slabs); the bound is what double-precision accumulation
+        # allows: 6 float32 roundings on the way from invstd to shift (the project's floor is 4 for one quantity), plus half
+        # the relative error of var + eps when q / n and mean^2 each carry 32 double roundings (at most 4 additions per thread
+        # for nslab <= 1024, 6 wave steps, 3 across the waves, the divisions and the product: 16, doubled).
+        c = CANCEL_COL
+        n = Fraction(count)
+        mean_x = sum(Fraction(float(x)) for x in slab[:, 0, c]) / n
+        qn_x = sum(Fraction(float(x)) for x in slab[:, 1, c]) / n
+        var_x = max(float(qn_x - mean_x * mean_x), 0.0)
+        invstd_x = 1.0 / (var_x + f32eps) ** 0.5
+        scale_x = float(gamma[c]) * invstd_x
+        want = dict(invstd=invstd_x, scale=scale_x, shift=float(beta[c]) - float(mean_x) * scale_x)
+        tol = 6 * 2.0 ** -24 + 0.5 * (32 * 2.0 ** -53 * (float(qn_x) + 2.0 * float(mean_x) ** 2)) / (var_x + f32eps)
+        errs = {k: abs(float(got[k][c].double()) - want[k]) / abs(want[k]) for k in want}
+        for k, e in errs.items():
+            print("TOL bnf_%s_cancel %s error %.3e  bound %.3e" % (k, tag, e, tol))
+        assert all(e <= tol for e in errs.values()), (errs, tol)
+    rep.assert_bars()
+
+    # backward finalize: (sum Gm, sum Gm yhat) partials, the forward's tables as inputs
+    bsl = (torch.randn(nslab, 2, C, generator=gen) * 3).to(F32)
+    scale, mean, invstd = (r64[k].to(F32) for k in ("scale", "mean", "invstd"))
+    m1, m2 = bsl.to(F64)[:, 0].sum(0), bsl.to(F64)[:, 1].sum(0)
+    a1, a2 = bsl.to(F64)[:, 0].abs().sum(0), bsl.to(F64)[:, 1].abs().sum(0)
+    for training in (1, 0):
+        g = Bufs()
+        bs, sc, mu, isd = g.fin(bsl), g.fin(scale), g.fin(mean), g.fin(invstd)
+        o = [g.fout((C,)) for _ in range(5)]
+        A.call("prifit_bn_bwd_finalize", A.ptr(bs), nslab, C, count, training, A.ptr(sc), A.ptr(mu), A.ptr(isd),
+               A.ptr(o[0]), A.ptr(o[1]), A.ptr(o[2]), A.ptr(o[3]), A.ptr(o[4]), A.cur_stream())
+        finite(*o)
+        g.intact()
+        b64 = bc.bn_bwd_finalize(m1, m2, count, training, scale, mean, invstd)
+        b32 = bc.bn_bwd_finalize(bsl[:, 0].sum(0), bsl[:, 1].sum(0), count, training, scale, mean, invstd, F32)
+        tg = tag + (training,)
+        rep.red("bnb_dgamma", tg, o[0], b64["dgamma"], b32["dgamma"], a2)
+        rep.red("bnb_dbeta", tg, o[1], b64["dbeta"], b32["dbeta"], a1)
+        assert torch.equal(o[2].cpu(), scale)
+        if training:
+            rep.ew("bnb_b", tg, o[3].cpu()[keep], b64["b"][keep], b32["b"][keep])
+            sd, md, id_ = scale.to(F64).abs(), mean.to(F64).abs(), invstd.to(F64)
+            rep.red("bnb_d", tg, o[4], b64["d"], b32["d"], sd * (md * id_ * a2 / count + a1 / count))
+        else:
+            assert not bool(o[3].any()) and not bool(o[4].any())
+        rep.assert_bars()
+
+
+@pytest.mark.parametrize("C,groups", sorted({c[:2] for c in bc.GN_CASES}) + [(100, 25)])
+def test_gn_finalize_kernels_in_guards_against_fp64(A, C, groups):
+    assert A.dll().prifit_gn_finalize_supported(C, groups) == 1
+    rep = bc.Report()
+    cpg = C // groups
+    for _, _, sps, Bs in [c for c in bc.GN_CASES if c[:2] == (C, groups)] or [(C, groups, 3, 5), (C, groups, 1, 1)]:
+        gen = bc.gen_of(bc.seed_of(7, C, groups, sps, Bs))
+        tag = (C, groups, sps, Bs)
+        rows = float(sps * bc.RED_ROWS)
+        m = rows * cpg
+        slab = stat_slabs(Bs * sps, C, gen)
+        gamma, beta = bc.signed(C, 0.5, 1.5, gen), bc.signed(C, 0.1, 1.0, gen)
+        offset = (0.5 * torch.randn(Bs, C, generator=gen)).to(F32)
+        s64, q64 = (slab.to(F64).view(Bs, sps, 2, C)[:, :, i].sum(1) for i in (0, 1))
+        s32, q32 = (slab.view(Bs, sps, 2, C)[:, :, i].sum(1) for i in (0, 1))
+        eps = 1e-5
+        for off in (None, offset):
+            g = Bufs()
+            sl, ga, be = g.fin(slab), g.fin(gamma), g.fin(beta)
+            o = [g.fout((Bs, C)) for _ in range(4)]
+            ch = g.dout((Bs, C))
+            if off is None:
+                o2 = [g.fout((Bs, C)) for _ in range(4)]
+                A.call("prifit_gn_finalize", A.ptr(sl), Bs, sps, C, groups, m, A.ptr(ga), A.ptr(be), eps, A.ptr(o2[0]), A.ptr(o2[1]),
+                       A.ptr(o2[2]), A.ptr(o2[3]), None, A.cur_stream())
+                A.call("prifit_gn_finalize", A.ptr(sl), Bs, sps, C, groups, m, A.ptr(ga), A.ptr(be), eps, A.ptr(o[0]), A.ptr(o[1]),
+                       A.ptr(o[2]), A.ptr(o[3]), A.ptr(ch), A.cur_stream())
+            else:
+                of = g.fin(off)
+                A.call("prifit_gn_finalize_offset", A.ptr(sl), Bs, sps, C, groups, m, A.ptr(ga), A.ptr(be), eps, A.ptr(of), rows,
+                       A.ptr(o[0]), A.ptr(o[1]), A.ptr(o[2]), A.ptr(o[3]), A.ptr(ch), A.cur_stream())
+            finite(ch, *o)
+            g.intact()
+            if off is None:
+                assert all(torch.equal(a, b) for a, b in zip(o, o2))     # the same tables with and without chsum
+            r64 = bc.gn_finalize(s64, q64, groups, m, gamma, beta, eps, off, rows)
+            r32 = bc.gn_finalize(s32, q32, groups, m, gamma, beta, eps, off, rows, F32)
+            nm = "gnf_" if off is None else "gnfo_"
+            for k, x in zip(("scale", "shift", "mean", "invstd"), o):
+                rep.ew(nm + k, tag, x, r64[k], r32[k])
+            rep.red(nm + "chsum", tag, ch, r64["chsum"], r32["chsum"], slab.to(F64).view(Bs, sps, 2, C)[:, :, 0].abs().sum(1))
+            rep.assert_bars()
+
+        # backward finalize and the parameter gradients, fed the float64 forward's tables and column sums
+        bsl = (torch.randn(Bs * sps, 2, C, generator=gen) * 3).to(F32)
+        mean, invstd = r64["mean"].to(F32), r64["invstd"].to(F32)
+        chsum = r64["chsum"]
+        t64 = [bsl.to(F64).view(Bs, sps, 2, C)[:, :, i].sum(1) for i in (0, 1)]
+        t32 = [bsl.view(Bs, sps, 2, C)[:, :, i].sum(1) for i in (0, 1)]
+        tabs = [bsl.to(F64).view(Bs, sps, 2, C)[:, :, i].abs().sum(1) for i in (0, 1)]
+        b64 = bc.gn_bwd_finalize(t64[0], t64[1], groups, m, gamma, mean, invstd, chsum, rows)
+        b32 = bc.gn_bwd_finalize(t32[0], t32[1], groups, m, gamma, mean, invstd, chsum, rows, F32)
+        res = {}
+        for with_sum in (False, True):
+            g = Bufs()
+            bs, ga, mu, isd = g.fin(bsl), g.fin(gamma), g.fin(mean), g.fin(invstd)
+            cb, cd, S = g.fout((Bs, C)), g.fout((Bs, C)), g.dout((Bs, 2, C))
+            chin = g.din(chsum) if with_sum else None
+            dsum = g.fout((Bs, C)) if with_sum else None
+            A.call("prifit_gn_bwd_finalize", A.ptr(bs), Bs, sps, C, groups, m, A.ptr(ga), A.ptr(mu), A.ptr(isd), A.ptr(cb),
+                   A.ptr(cd), A.ptr(S), A.ptr(chin), rows, A.ptr(dsum), A.cur_stream())
+            dg, db_, dbias = g.fout((C,)), g.fout((C,)), (g.fout((C,)) if with_sum else None)
+            Sin = g.din(b64["S"].reshape(Bs, 2 * C)).view(Bs, 2, C)
+            dsin = g.fin(b64["dsum"].to(F32)) if with_sum else None
+            A.call("prifit_gn_param_grads", A.ptr(Sin), Bs, C, A.ptr(dg), A.ptr(db_), A.ptr(dsin), A.ptr(dbias), A.cur_stream())
+            finite(cb, cd, S, dg, db_)
+            g.intact()
+            res[with_sum] = (cb.clone(), cd.clone(), S.clone())
+            tg = tag + (int(with_sum),)
+            gd, isd64, mu64 = gamma.to(F64).abs(), invstd.to(F64), mean.to(F64).abs()
+            am1 = ((gd * tabs[0]).view(Bs, groups, cpg).sum(-1) / m).repeat_interleave(cpg, 1)
+            am2 = ((gd * tabs[1]).view(Bs, groups, cpg).sum(-1) / m).repeat_interleave(cpg, 1)
+            rep.ew("gnb_cb", tg, cb, b64["cb"], b32["cb"])
+            rep.red("gnb_cd", tg, cd, b64["cd"], b32["cd"], isd64 * am1 + mu64 * isd64 * isd64 * am2)
+            rep.red("gnb_S", tg, S, b64["S"], b32["S"], torch.stack(tabs, 1))
+            p64, p32 = bc.param_grads(b64["S"], b64["dsum"].to(F32)), bc.param_grads(b64["S"], b64["dsum"].to(F32), F32)
+            rep.red("gnp_dgamma", tg, dg, p64["dgamma"], p32["dgamma"], b64["S"][:, 1].abs().sum(0))
+            rep.red("gnp_dbeta", tg, db_, p64["dbeta"], p32["dbeta"], b64["S"][:, 0].abs().sum(0))
+            if with_sum:
+                finite(dsum, dbias)
+                ca = (gamma * invstd).to(F64).abs()
+                rep.red("gnb_dsum", tg, dsum, b64["dsum"], b32["dsum"],
+                        ca * tabs[0] + b64["cb"].abs() * chsum.abs() + b64["cd"].abs() * rows)
+                rep.red("gnp_db", tg, dbias, p64["db"], p32["db"], b64["dsum"].to(F32).to(F64).abs().sum(0))
+            rep.assert_bars()
+        assert all(torch.equal(a, b) for a, b in zip(res[False], res[True]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# element-wise passes
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", sorted({c[1] for c in bc.ELEMENT_CASES}))
+def test_affine_relu_and_bwd_apply_in_guards_against_fp64(A, C):
+    rep = bc.Report()
+    for P, _, rps, slope in [c for c in bc.ELEMENT_CASES if c[1] == C]:
+        case = bc.element_case(P, C, rps, slope)
+        tag = (P, C, rps, slope)
+        g = Bufs()
+        Y, Gr = g.fin(case["Y"], ld_of(C, 0)), g.fin(case["G"], ld_of(C, 1))
+        sc, sh, ca, cb, cd = tabs_in(g, case, ("scale", "shift", "a", "b", "d"))
+        wide = C + 12
+        out, out2 = g.mout(P, C, wide + 4, 8, wide), g.mout(P, C, wide + 4, 8, wide)       # a column slice of a wider buffer
+        for o in (out, out2):
+            A.call("prifit_affine_relu", A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), P, C, rps, slope, A.ptr(o),
+                   LL(o.stride(0)), A.cur_stream())
+        dY, dY2 = g.mout(P, C, ld_of(C, 2)), g.mout(P, C, ld_of(C, 2))
+        for o in (dY, dY2):
+            A.call("prifit_bn_relu_bwd_apply", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh),
+                   A.ptr(ca), A.ptr(cb), A.ptr(cd), P, C, rps, slope, A.ptr(o), LL(o.stride(0)), A.cur_stream())
+        finite(out, dY)
+        g.intact()                                             # pad columns and the columns beside the slice included
+        assert torch.equal(out, out2) and torch.equal(dY, dY2)
+        rep.ew("affine", tag, out, bc.affine_act(case["Y"], case["scale"], case["shift"], rps, slope),
+               bc.affine_act(case["Y"], case["scale"], case["shift"], rps, slope, F32))
+        r = {}
+        for dt in (F64, F32):
+            Gm = bc.masked_grad(case["G"], case["Y"], case["scale"], case["shift"], rps, slope, dt)
+            r[dt] = bc.apply_bwd(Gm, case["Y"], case["a"], case["b"], case["d"], rps, dt)
+        rep.ew("apply_dY", tag, dY, r[F64], r[F32])
+        rep.assert_bars()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# group max-pool: forward, backward apply (both kernels), the sparse table
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", sorted({c[1] for c in bc.POOL_CASES}))
+def test_pool_fwd_bwd_apply_and_table_in_guards_against_fp64(A, K):
+    rep = bc.Report()
+    ties = 0
+    for G, _, C, m, slope in [c for c in bc.POOL_CASES if c[1] == K]:
+        rps = m * K
+        case = bc.pool_case(G, K, C, rps, slope)
+        tag = (G, K, C, rps, slope)
+        o64, arg64 = bc.pool_fwd(case["Y"], case["scale"], case["shift"], G, K, rps, slope)
+        o32, _ = bc.pool_fwd(case["Y"], case["scale"], case["shift"], G, K, rps, slope, F32)
+        g = Bufs()
+        Y, gp = g.fin(case["Y"], ld_of(C, 0)), g.fin(case["gp"], ld_of(C, 1))
+        sc, sh, ca, cb, cd = tabs_in(g, case, ("scale", "shift", "a", "b", "d"))
+        wide = C + 8
+        out, arg = g.mout(G, C, wide + 12, 4, wide), g.iout((G, C))
+        out2, arg2 = g.mout(G, C, wide + 12, 4, wide), g.iout((G, C))
+        for o, a in ((out, arg), (out2, arg2)):
+            A.call("prifit_pool_fwd", A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), G, K, C, rps, slope, A.ptr(o),
+                   LL(o.stride(0)), A.ptr(a), A.cur_stream())
+        ai = g.iin(arg64, 0)
+        dY, dY2 = g.mout(G * K, C, ld_of(C, 3)), g.mout(G * K, C, ld_of(C, 3))
+        for o in (dY, dY2):
+            A.call("prifit_pool_bwd_apply", A.ptr(gp), LL(gp.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(ai), A.ptr(sc), A.ptr(sh),
+                   A.ptr(ca), A.ptr(cb), A.ptr(cd), G, K, C, rps, slope, A.ptr(o), LL(o.stride(0)), A.cur_stream())
+        T = None
+        if rps == 0:
+            T = g.fout((G, C))
+            A.call("prifit_pool_bwd_table", A.ptr(gp), LL(gp.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(ai), A.ptr(sc), A.ptr(sh),
+                   A.ptr(ca), G, K, C, slope, A.ptr(T), A.cur_stream())
+            finite(T)
+        finite(out, dY)
+        g.intact()
+        argc = arg.cpu().long()
+        assert torch.equal(argc, arg64), "arg is not the first maximum"
+        if K > 1:
+            assert not bool(argc[:, 1].any())                  # scale == 0 in channel 1: every row ties, the first wins
+            yv = case["Y"].view(G, K, C)[..., :4]            # a duplicated row is equal in every channel
+            ties += int((yv.unsqueeze(1) == yv.unsqueeze(2)).all(-1).sum()) - G * K
+        assert torch.equal(out, out2) and torch.equal(arg, arg2) and torch.equal(dY, dY2)
+        rep.ew("pool_out", tag, out, o64, o32)
+        r = {}
+        for dt in (F64, F32):
+            Gm = bc.pooled_grad(case["gp"], case["Y"], arg64, case["scale"], case["shift"], G, K, rps, slope, dt)
+            r[dt] = bc.apply_bwd(Gm, case["Y"], case["a"], case["b"], case["d"], rps, dt)
+        rep.ew("pool_dY", tag, dY, r[F64], r[F32])
+        if T is not None:
+            rep.ew("pool_table", tag, T,
+                   bc.pool_bwd_table(case["gp"], case["Y"], arg64, case["scale"], case["shift"], case["a"], G, K, slope),
+                   bc.pool_bwd_table(case["gp"], case["Y"], arg64, case["scale"], case["shift"], case["a"], G, K, slope, F32))
+        rep.assert_bars()
+    assert K == 1 or ties > 0                                   # the table does hold duplicated rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# column sums
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", sorted({c[1] for c in bc.COLSUM_CASES}))
+def test_col_sum_in_guards_against_fp64(A, C):
+    rep = bc.Report()
+    cases = [(P, 0) for P, c in bc.COLSUM_CASES if c == C] + [(3 * bc.CS_ROWS, bc.CS_ROWS)]
+    for P, rps in cases:
+        gen = bc.gen_of(bc.seed_of(8, P, C, rps))
+        Yc = (0.2 + torch.randn(P, C, generator=gen)).to(F32)
+        g = Bufs()
+        Y = g.fin(Yc, ld_of(C, P % 2))
+        nout = P // rps if rps else 1
+        ws = A.dll().prifit_col_sum_workspace(P, C)
+        assert ws == -(-P // bc.CS_ROWS) * C
+        res = []
+        for _ in range(2):
+            out, work = g.fout((nout, C)), g.fout((ws,))
+            if rps:
+                A.call("prifit_col_sum_samples", A.ptr(Y), LL(Y.stride(0)), P, C, rps, A.ptr(out), A.ptr(work), A.cur_stream())
+            else:
+                A.call("prifit_col_sum", A.ptr(Y), LL(Y.stride(0)), P, C, A.ptr(out), A.ptr(work), A.cur_stream())
+            res.append(out)
+        finite(*res)
+        g.intact()
+        assert torch.equal(res[0], res[1])
+        ab = Yc.to(F64).abs()
+        if rps:
+            rep.red("col_sum_smp", (P, C, rps), res[0], bc.col_sum_samples(Yc, rps), bc.col_sum_samples(Yc, rps, F32),
+                    ab.view(-1, rps, C).sum(1))
+        else:
+            rep.red("col_sum", (P, C), res[0], bc.col_sum(Yc).unsqueeze(0), bc.col_sum(Yc, F32).unsqueeze(0), ab.sum(0, keepdim=True))
+        rep.assert_bars()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the by-linearity first layer and its backward forms
+# ---------------------------------------------------------------------------------------------------------------------------
+def _grads(case, dY64, dY32, terms=None):
+    """float64 / float32 (dU, dVc) by autograd of the forward restatement, and the float64 sums of |terms|: the rows of dY, or,
+    where the kernel forms dY = a Gm + b Y + d itself, |a Gm| + |b Y| + |d| of every row (`terms`)"""
+    r64 = bc.gather_linear_grads(case["U"], case["Vc"], case["bias"], case["idx"], dY64)
+    r32 = bc.gather_linear_grads(case["U"], case["Vc"], case["bias"], case["idx"], dY32, F32)
+    ab = bc.gather_linear_grads(case["U"], case["Vc"], case["bias"], case["idx"], dY64.abs() if terms is None else terms)
+    return r64, r32, (ab[0], ab[1].abs())
+
+
+def _terms(Gm, Y, t, rps):
+    """|a Gm| + |b Y| + |d| per element, float64"""
+    P = Y.shape[0]
+    return ((bc.tab(t["a"].to(F64), P, rps) * Gm.to(F64)).abs() + (bc.tab(t["b"].to(F64), P, rps) * Y.to(F64)).abs()
+            + bc.tab(t["d"].to(F64), P, rps).abs())
+
+
+def u_in(g, case):
+    """U in guards, the row of the point no list names (N - 1) NaN"""
+    U = g.fin(case["U"])
+    U[:, case["N"] - 1] = NAN
+    return U
+
+
+def _variation(name, tag, a, b, absum):
+    """Largest difference between two runs of a kernel that adds with float atomics, in the unit of the bars (recorded in the
+    module docstring, not asserted)"""
+    print("VAR %-14s %-34s %.3e" % (name, tag, bc.red_err(a, b.cpu().to(F64), absum)))
+
+
+def _check_grads(rep, name, tag, case, dU, dVc, dY64, dY32, terms=None):
+    finite(dU, dVc)
+    r64, r32, ab = _grads(case, dY64, dY32, terms)
+    B, N, C = case["B"], case["N"], case["C"]
+    used = torch.zeros(B, N, dtype=torch.bool)
+    idx = case["idx"].long()
+    ok = (idx >= 0) & (idx < N)
+    used[torch.arange(B).view(B, 1, 1).expand_as(idx)[ok], idx[ok]] = True
+    assert not bool(dU.cpu()[~used].any()), "dU of a point no list names is not zero"
+    rep.red(name + "_dU", tag, dU, r64[0], r32[0], ab[0])
+    rep.red(name + "_dVc", tag, dVc, r64[1], r32[1], ab[1])
+    return ab
+
+
+@pytest.mark.parametrize("oob", [False, True], ids=["in_range", "out_of_range"])
+@pytest.mark.parametrize("N,S,K", bc.GATHER_SHAPES)
+def test_gather_linear_and_its_backward_forms_in_guards_against_fp64(A, N, S, K, oob):
+    rep = bc.Report()
+    B = bc.GATHER_B
+    for C, bias in [(C, b) for C in sorted(set(bc.GATHER_C_GENERIC + bc.GATHER_C_STAGED)) for b in (True, False)]:
+        slope = 0.2
+        case = bc.gather_case(N, S, K, C, bias=bias, oob=oob, slope=slope)
+        P, idx = case["P"], case["idx"]
+        tag = (N, S, K, C, int(bias), int(oob))
+        Y64 = bc.gather_linear(case["U"].to(F64), case["Vc"].to(F64), case["bias"], idx).view(P, C)
+        Y32 = bc.gather_linear(case["U"], case["Vc"], case["bias"], idx, F32).view(P, C)
+        Yr = case["Y"]                                          # the float64 forward rounded to float32
+        assert torch.equal(Yr, Y64.to(F32))
+        g = Bufs()
+        # the guards around idx hold point N - 1, which no list names and whose row of U is NaN on the device
+        ix = g.iin(idx, N - 1)
+        assert not bool((idx == N - 1).any())
+        if C % 4 == 0:
+            U, Vc = u_in(g, case), g.fin(case["Vc"])
+            bv = g.fin(case["bias"]) if bias else None
+            nslab = -(-P // bc.RED_ROWS)
+            res = []
+            for _ in range(2):
+                Yo, slab = g.fout((P, C)), g.fout((nslab, 2, C))
+                A.call("prifit_gather_linear_fwd", A.ptr(U), A.ptr(Vc), A.ptr(bv), A.ptr(ix), B, N, S, K, C, A.ptr(Yo), A.ptr(slab),
+                       A.cur_stream())
+                res.append((Yo, slab))
+            finite(*res[0])
+            g.intact()
+            assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
+            bad = ((idx < 0) | (idx >= N)).view(P)
+            if bool(bad.any()):                                 # an out-of-range row is the bias alone
+                want = case["bias"] if bias else torch.zeros(C)     # without a bias exactly 0
+                assert bool((res[0][0].cpu()[bad] == want).all())
+            rep.ew("gl_Y", tag, res[0][0], Y64, Y32)
+            rep.red("gl_slab", tag, res[0][1], bc.col_stats(Y64), bc.col_stats(Y32, dtype=F32),
+                    bc.slab_sums(Y64.abs(), Y64 * Y64, bc.RED_ROWS))
+        if C in bc.GATHER_C_GENERIC:
+            # plain: dY given
+            Gd = g.fin(case["G"])
+            run = []
+            for _ in range(2):
+                dU, dVc = g.fout((B, N, C), zero=True), g.fout((B, S, C))
+                A.call("prifit_gather_linear_bwd", A.ptr(Gd), A.ptr(ix), B, N, S, K, C, A.ptr(dU), A.ptr(dVc), A.cur_stream())
+                run.append((dU, dVc))
+            g.intact()
+            ab = _check_grads(rep, "glb", tag, case, run[0][0], run[0][1], case["G"].to(F64), case["G"])
+            assert torch.equal(run[0][1], run[1][1])            # dVc: no atomics
+            _variation("glb_dU", tag, run[0][0], run[1][0], ab[0])
+            # pooled: per-sample tables, the winners of the float64 pool
+            t = case["gn"]
+            rps, arg = S * K, case["arg"].long()
+            gp, Yi, ai = g.fin(case["gp"], ld_of(C, 0)), g.fin(Yr), g.iin(case["arg"], 0)
+            sc, sh, ca, cb, cd = tabs_in(g, t, ("scale", "shift", "a", "b", "d"))
+            run = []
+            for _ in range(2):
+                dU, dVc = g.fout((B, N, C), zero=True), g.fout((B, S, C))
+                A.call("prifit_gather_linear_bwd_pool", A.ptr(gp), LL(gp.stride(0)), A.ptr(Yi), A.ptr(ai), A.ptr(sc), A.ptr(sh),
+                       A.ptr(ca), A.ptr(cb), A.ptr(cd), A.ptr(ix), B, N, S, K, C, rps, slope, A.ptr(dU), A.ptr(dVc),
+                       A.cur_stream())
+                run.append((dU, dVc))
+            g.intact()
+            d = {}
+            for dt in (F64, F32):
+                Gm = bc.pooled_grad(case["gp"], Yr, arg, t["scale"], t["shift"], B * S, K, rps, slope, dt)
+                d[dt] = bc.apply_bwd(Gm, Yr, t["a"], t["b"], t["d"], rps, dt)
+                if dt == F64:
+                    tm = _terms(Gm, Yr, t, rps)
+            ab = _check_grads(rep, "glp", tag, case, run[0][0], run[0][1], d[F64], d[F32], tm)
+            assert torch.equal(run[0][1], run[1][1])
+            _variation("glp_dU", tag, run[0][0], run[1][0], ab[0])
+        if C in bc.GATHER_C_STAGED:
+            t = case["bn"]
+            assert A.dll().prifit_gather_linear_bwd_bn_supported(N, C) == 1
+            assert A.dll().prifit_gather_linear_bwd_csr_supported(N, C) == 1
+            Gd, Yi = g.fin(case["G"]), g.fin(Yr)
+            sc, sh, ca, cb, cd = tabs_in(g, t, ("scale", "shift", "a", "b", "d"))
+            d = {}
+            for dt in (F64, F32):
+                Gm = bc.masked_grad(case["G"], Yr, t["scale"], t["shift"], 0, 0.0, dt)
+                d[dt] = bc.apply_bwd(Gm, Yr, t["a"], t["b"], t["d"], 0, dt)
+                if dt == F64:
+                    tm = _terms(Gm, Yr, t, 0)
+            run = []
+            for _ in range(2):
+                dU, dVc = g.fout((B, N, C), zero=True), g.fout((B, S, C), zero=True)
+                A.call("prifit_gather_linear_bwd_bn", A.ptr(Gd), A.ptr(Yi), A.ptr(sc), A.ptr(sh), A.ptr(ca), A.ptr(cb), A.ptr(cd),
+                       A.ptr(ix), B, N, S, K, C, A.ptr(dU), A.ptr(dVc), A.cur_stream())
+                run.append((dU, dVc))
+            g.intact()
+            ab = _check_grads(rep, "glbn", tag, case, run[0][0], run[0][1], d[F64], d[F32], tm)
+            _variation("glbn_dU", tag, run[0][0], run[1][0], ab[0])
+            _variation("glbn_dVc", tag, run[0][1], run[1][1], ab[1])
+            # the gather form: y re-formed from U, Vc, bias; no atomics
+            U, Vc = u_in(g, case), g.fin(case["Vc"])
+            bv = g.fin(case["bias"]) if bias else None
+            E = S * K
+            offs, lst, pos, own = g.iout((B, N + 1)), g.iout((B, E)), g.iout((B, E)), g.iout((B, E))
+            A.call("prifit_list_csr", A.ptr(ix), B, N, E, A.ptr(offs), A.ptr(lst), A.ptr(pos), A.ptr(own), A.cur_stream())
+            ws = A.dll().prifit_gather_linear_bwd_csr_workspace(B, S, K, C)
+            res = []
+            for _ in range(2):
+                dU, dVc, work = g.fout((B, N, C)), g.fout((B, S, C)), g.dout((ws,))
+                A.call("prifit_gather_linear_bwd_csr", A.ptr(Gd), A.ptr(U), A.ptr(Vc), A.ptr(bv), A.ptr(sc), A.ptr(sh), A.ptr(ca),
+                       A.ptr(cb), A.ptr(cd), A.ptr(ix), A.ptr(offs), A.ptr(lst), A.ptr(own), B, N, S, K, C, A.ptr(dU), A.ptr(dVc),
+                       A.ptr(work), A.cur_stream())
+                res.append((dU, dVc))
+            g.intact()
+            oc = offs.cpu().long()
+            ok = (idx >= 0) & (idx < N)
+            assert torch.equal(oc[:, -1], ok.view(B, -1).sum(1)) and bool((oc[:, 1:] >= oc[:, :-1]).all())
+            assert torch.equal(res[0][1], res[1][1])            # dVc: slot order.  (dU: the order inside a CSR list is not fixed)
+            for dt, Yx in ((F64, Y64), (F32, Y32)):
+                Gm = bc.masked_grad(case["G"], Yx, t["scale"], t["shift"], 0, 0.0, dt)
+                d[dt] = bc.apply_bwd(Gm, Yx, t["a"], t["b"], t["d"], 0, dt)
+                if dt == F64:
+                    tm = _terms(Gm, Yx, t, 0)
+            ab = _check_grads(rep, "glcsr", tag, case, res[0][0], res[0][1], d[F64], d[F32], tm)
+            _variation("glcsr_dU", tag, res[0][0], res[1][0], ab[0])
+        rep.assert_bars()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# whole layers, the kernels' own outputs end to end
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c[0] for c in bc.CHAIN_CASES])
+def test_whole_layer_in_guards_against_fp64(A, name):
+    rep = bc.Report()
+    case = bc.chain_case(name)
+    P, C, rps, slope, pool, norm = case["P"], case["C"], case["rps"], case["slope"], case["pool"], case["norm"]
+    bn = norm == "bn"
+    f64, o64, arg64 = bc.chain_forward(case, case["Y"])
+    f32, o32, _ = bc.chain_forward(case, case["Y"], F32)
+    b64 = bc.chain_backward(case, case["Y"], f64, arg64, case["gout"])
+    b32 = bc.chain_backward(case, case["Y"], f32, arg64, case["gout"], F32)
+    g = Bufs()
+    Y = g.fin(case["Y"], ld_of(C, 0))
+    ga, be = g.fin(case["gamma"]), g.fin(case["beta"])
+    nslab = -(-P // bc.RED_ROWS)
+    slab = g.fout((nslab, 2, C))
+    A.call("prifit_col_stats", A.ptr(Y), LL(Y.stride(0)), P, C, A.ptr(slab), A.cur_stream())
+    nt = 1 if bn else case["samples"]
+    sc, sh, mu, isd = (g.fout((nt, C)) for _ in range(4))
+    if bn:
+        rm, rv = g.fout((C,), init=case["rmean"]), g.fout((C,), init=case["rvar"])
+        A.call("prifit_bn_finalize", A.ptr(slab), nslab, C, float(P), A.ptr(ga), A.ptr(be), bc.BN_EPS, bc.BN_MOMENTUM, A.ptr(rm),
+               A.ptr(rv), A.ptr(sc), A.ptr(sh), A.ptr(mu), A.ptr(isd), A.cur_stream())
+    else:
+        sps, cnt = rps // bc.RED_ROWS, float(rps * (C // case["groups"]))
+        ch = g.dout((nt, C))
+        if case["offset"] is not None:
+            of = g.fin(case["offset"])
+            A.call("prifit_gn_finalize_offset", A.ptr(slab), nt, sps, C, case["groups"], cnt, A.ptr(ga), A.ptr(be), bc.GN_EPS,
+                   A.ptr(of), float(rps), A.ptr(sc), A.ptr(sh), A.ptr(mu), A.ptr(isd), A.ptr(ch), A.cur_stream())
+        else:
+            A.call("prifit_gn_finalize", A.ptr(slab), nt, sps, C, case["groups"], cnt, A.ptr(ga), A.ptr(be), bc.GN_EPS, A.ptr(sc),
+                   A.ptr(sh), A.ptr(mu), A.ptr(isd), A.ptr(ch), A.cur_stream())
+    Gr = g.fin(case["gout"], ld_of(C, 1))
+    dY = g.mout(P, C, ld_of(C, 3))
+    if pool:
+        G, K = pool
+        out, arg = g.mout(G, C, ld_of(C, 2)), g.iout((G, C))
+        A.call("prifit_pool_fwd", A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), G, K, C, rps, slope, A.ptr(out),
+               LL(out.stride(0)), A.ptr(arg), A.cur_stream())
+        nb = -(-G // bc.POOL_RED_ROWS)
+        bslab = g.fout((nb, 2, C))
+        A.call("prifit_pool_bwd_reduce", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(arg), A.ptr(sc), A.ptr(sh),
+               A.ptr(mu), A.ptr(isd), G, K, C, rps, slope, A.ptr(bslab), A.cur_stream())
+    else:
+        out = g.mout(P, C, ld_of(C, 2))
+        A.call("prifit_affine_relu", A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), P, C, rps, slope, A.ptr(out),
+               LL(out.stride(0)), A.cur_stream())
+        nb = nslab
+        bslab = g.fout((nb, 2, C))
+        A.call("prifit_bn_relu_bwd_reduce", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), A.ptr(mu),
+               A.ptr(isd), P, C, rps, slope, A.ptr(bslab), A.cur_stream())
+    dg, db_ = g.fout((C,)), g.fout((C,))
+    cb, cd = g.fout((nt, C)), g.fout((nt, C))
+    dsum = None
+    if bn:
+        ca = g.fout((C,))
+        A.call("prifit_bn_bwd_finalize", A.ptr(bslab), nb, C, float(P), 1, A.ptr(sc), A.ptr(mu), A.ptr(isd), A.ptr(dg), A.ptr(db_),
+               A.ptr(ca), A.ptr(cb), A.ptr(cd), A.cur_stream())
+    else:
+        ca = sc
+        S, dsum, dbias = g.dout((nt, 2, C)), g.fout((nt, C)), g.fout((C,))
+        A.call("prifit_gn_bwd_finalize", A.ptr(bslab), nt, nb // nt, C, case["groups"], cnt, A.ptr(ga), A.ptr(mu), A.ptr(isd),
+               A.ptr(cb), A.ptr(cd), A.ptr(S), A.ptr(ch), float(rps), A.ptr(dsum), A.cur_stream())
+        A.call("prifit_gn_param_grads", A.ptr(S), nt, C, A.ptr(dg), A.ptr(db_), A.ptr(dsum), A.ptr(dbias), A.cur_stream())
+    if pool:
+        A.call("prifit_pool_bwd_apply", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(arg), A.ptr(sc), A.ptr(sh),
+               A.ptr(ca), A.ptr(cb), A.ptr(cd), G, K, C, rps, slope, A.ptr(dY), LL(dY.stride(0)), A.cur_stream())
+    else:
+        A.call("prifit_bn_relu_bwd_apply", A.ptr(Gr), LL(Gr.stride(0)), A.ptr(Y), LL(Y.stride(0)), A.ptr(sc), A.ptr(sh), A.ptr(ca),
+               A.ptr(cb), A.ptr(cd), P, C, rps, slope, A.ptr(dY), LL(dY.stride(0)), A.cur_stream())
+    finite(sc, sh, mu, isd, out, dY, dg, db_, cb, cd)
+    g.intact()
+    if pool:
+        assert torch.equal(arg.cpu().long(), arg64)
+        assert not bool(arg.cpu()[:, 1].any())                  # gamma == 0 in channel 1
+    for k, x in (("scale", sc), ("shift", sh), ("mean", mu), ("invstd", isd)):
+        rep.ew("layer_" + k, name, x.view(nt, C), f64[k].view(nt, C), f32[k].view(nt, C))
+    if bn:
+        rep.ew("layer_rmean", name, rm, f64["rmean"], f32["rmean"])
+        rep.ew("layer_rvar", name, rv, f64["rvar"], f32["rvar"])
+    rep.ew("layer_out", name, out, o64, o32)
+    rep.ew("layer_dY", name, dY, b64[0], b32[0])
+    if pool:
+        Gm = bc.pooled_grad(case["gout"], case["Y"], arg64, f64["scale"], f64["shift"], pool[0], pool[1], rps, slope)
+    else:
+        Gm = bc.masked_grad(case["gout"], case["Y"], f64["scale"], f64["shift"], rps, slope)
+    t0, t1 = bc.bwd_terms(Gm, case["Y"], f64["mean"], f64["invstd"], rps)
+    rep.red("layer_dgamma", name, dg, b64[1], b32[1], t1.abs().sum(0))
+    rep.red("layer_dbeta", name, db_, b64[2], b32[2], t0.abs().sum(0))
+    if dsum is not None:
+        # the offset's gradient = the column sums of dY per sample, here from the float64 dY itself
+        col = b64[0].view(nt, rps, C).sum(1)
+        assert bc.red_err(b64[3], col, b64[0].abs().view(nt, rps, C).sum(1)) < 1e-12
+        rep.red("layer_dsum", name, dsum, col, b32[3], b64[0].abs().view(nt, rps, C).sum(1))
+        rep.red("layer_db", name, dbias, col.sum(0), b32[3].sum(0), b64[0].abs().sum(0))
+    rep.assert_bars()

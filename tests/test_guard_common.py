@@ -4,7 +4,7 @@ import math
 import pytest
 import torch
 
-from guard_common import (ALIGN, SENTINEL, assert_guards_intact, guarded, guarded_like, padded_stream, poison_bits, x_tail)
+from guard_common import (ALIGN, SENTINEL, assert_guards_intact, guarded, guarded_like, guarded_matrix, padded_stream, poison_bits, x_tail)
 
 
 def test_guarded_view_alignment_contiguity_and_poison():
@@ -75,3 +75,26 @@ def test_assert_guards_intact_catches_one_word(where):
     assert_guards_intact(base, inner)
     inner[(0,) * inner.dim()] = float("nan")                 # the view itself is not a guard
     assert_guards_intact(base, inner)
+
+
+def test_guarded_matrix_layout():
+    for P, C, ld, lead, tail in ((300, 12, 20, 7, 129 * 20), (1, 4, 4, 0, 1), (5, 8, 1032, 64, 129 * 1032)):
+        m, base = guarded_matrix(P, C, ld, lead, tail, poison=SENTINEL, device="cpu")
+        assert m.shape == (P, C) and m.stride() == (ld, 1) and m.data_ptr() % ALIGN == 0
+        s = m.storage_offset() - base.storage_offset()
+        assert s >= lead and base.numel() - s - P * ld >= tail
+        bits = base.view(torch.int32)
+        assert (bits == SENTINEL).all()                     # the view too, until filled
+        m.fill_(3.0)
+        assert int((base == 3.0).sum()) == P * C and int((bits == SENTINEL).sum()) == base.numel() - P * C
+        for r in range(P):                                  # element (r, c) at r * ld + c; the pad columns of EVERY row hold poison
+            row = base[s + r * ld:s + (r + 1) * ld]
+            assert (row[:C] == 3.0).all() and (row[C:].view(torch.int32) == SENTINEL).all()
+        assert (bits[:s] == SENTINEL).all() and (bits[s + P * ld:] == SENTINEL).all()
+        assert_guards_intact(base, m)
+        if ld > C:
+            bits[s + (P - 1) * ld + C] = SENTINEL ^ 1       # a pad column of the last row
+            with pytest.raises(AssertionError, match="1 guard word"):
+                assert_guards_intact(base, m)
+    with pytest.raises(AssertionError):
+        guarded_matrix(4, 8, 7, 0, 0, device="cpu")
