@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 700
+#define PRIFIT_ABI_VERSION 800
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1016,6 +1016,40 @@ int prifit_affine_points(const float *src, int B, int M, int C, const float *aff
 int prifit_seg_metrics(const float *scores, long long ld, const long long *target, int B, int N, int P,
                        const int32_t *cat_of_label, int restricted, long long *pred, int32_t *shape_cat, int32_t *inter,
                        int32_t *uni, long long *totals, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
+/* frozen inference (prifit_amd/inference.py): BatchNorm folded into the weights, MLP chains on chip  */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Folds the eval-mode BatchNorm of every (conv1x1 + BatchNorm) layer of a network into the convolution, ONE launch for up
+ * to prifit_fold_bn_max_jobs() layers (HOST arrays of njobs entries each, read before the call returns; the jobs travel by
+ * value like those of prifit_pack_cols_multi).  Job j: W [cout, kin] contiguous, bias [cout] or NULL (= 0), gamma / beta /
+ * mean / var [cout] (the BatchNorm's weight, bias, running_mean, running_var), eps.  Into the flat buffer `flat` (flat_len
+ * floats, 16-byte aligned) it writes
+ *   W' [cout, ldw] at flat + w_off:  W'[c][k] = W[c][k] * s_c, s_c = gamma[c] / sqrtf(var[c] + eps); columns kin .. ldw - 1 = 0;
+ *   b' [cout]      at flat + b_off:  b'[c] = (bias[c] - mean[c]) * s_c + beta[c]
+ * (every operation rounded once, no fused multiply-add).  ldw % 4 == 0 and w_off % 4 == 0: every W' row starts 16-byte aligned.
+ * gamma NULL: a layer without BatchNorm, W' = W and b' = bias bit for bit.  The regions of different jobs must not overlap. */
+int prifit_fold_bn_max_jobs(void);
+int prifit_fold_bn(int njobs, const float *const *W, const int32_t *cout, const int32_t *kin, const float *const *bias,
+                   const float *const *gamma, const float *const *beta, const float *const *mean, const float *const *var,
+                   const float *eps, const long long *w_off, const int32_t *ldw, const long long *b_off, float *flat,
+                   long long flat_len, void *stream);
+
+/* Layers 2 and 3 of a set-abstraction scale and its max-pool in one launch, on folded weights (models/pointnet_util.py:
+ * 250-257 in eval mode):  out[g][c] = max over the pool_K rows r of group g of relu(W2 relu(W1 relu(X[r]) + b1) + b2)[c].
+ * X [G * pool_K, ldx] are the first layer's folded pre-activations (as prifit_sa_group_linear_fwd writes them when given
+ * the folded first-layer weight), C0 wide; W1 [C1, ldw1], b1 [C1], W2 [C2, ldw2], b2 [C2] as prifit_fold_bn writes them;
+ * out [G, ldo] is a column window like prifit_pool_fwd's (ldo >= C2).  No [P, C1] or [P, C2] tensor is written: a wave keeps
+ * its 32 rows in registers from the load to the maximum (v_mfma_f32_32x32x2_f32, fp32 accumulation).
+ * prifit_mlp_chain_pool_supported: 1 for (C0, C1, C2) in (32,32,64), (64,64,128), (64,96,128), (128,128,256), (128,196,256)
+ * with pool_K in {32, 64, 128}, any G; 0 otherwise.  prifit_mlp_chain_pool_workspace: floats of `workspace` the call needs
+ * (0 today: workspace may be NULL).  X, W1, b1, W2, b2 16-byte aligned, ldx / ldw1 / ldw2 multiples of 4. */
+int prifit_mlp_chain_pool_supported(int C0, int C1, int C2, int pool_K);
+long long prifit_mlp_chain_pool_workspace(int G, int pool_K, int C0, int C1, int C2);
+int prifit_mlp_chain_pool_f32(const float *X, long long ldx, int G, int pool_K, int C0, int C1, int C2, const float *W1,
+                              long long ldw1, const float *b1, const float *W2, long long ldw2, const float *b2, float *out,
+                              long long ldo, float *workspace, void *stream);
 
 #ifdef __cplusplus
 }

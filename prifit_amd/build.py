@@ -39,6 +39,7 @@ SOURCES = {
     "optim.hip": [],
     "augment.hip": ["-ffp-contract=off"],
     "seg_metrics.hip": [],
+    "infer.hip": [],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],
     "comm.hip": [],        # host-only: the RCCL export (RCCL itself is resolved with dlopen at run time)

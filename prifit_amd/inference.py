@@ -1,0 +1,373 @@
+"""Frozen inference for the MSG part-segmentation network.
+
+    frozen = prifit_amd.inference.freeze(model)      # models.pointnet2_part_seg_msg.get_model, reconstruct=False
+    seg, (l1, l2, l3), feat, zero, zero = frozen(xyz, cls_label, fps_start=None)
+    seg = frozen.predict(xyz, cls_label)             # [B, N, num_parts] log-probabilities
+    frozen.refresh()                                 # re-fold from the live model (after more training)
+
+With fixed statistics a BatchNorm is a per-channel affine: s = gamma / sqrt(var + eps), bn(W x + b) = (s W) x + ((b - mean) s + beta).
+freeze() folds every layer of the network into ONE flat fp32 buffer with one launch (prifit_fold_bn) and brings the first-layer
+weights that are consumed column-permuted into the internal row layouts with the existing pack launch (prifit_pack_cols_multi).
+The forward then runs on that buffer alone, under no_grad:
+  * sampling, ball query + grouping + first conv (prifit_sa_group_linear_fwd), 3-NN, prifit_fp_rows: the entry points of the
+    live model, given the folded weights -- the index lists are the live model's, bit for bit;
+  * layers 2 and 3 of every SA1 / SA2 scale and the max over the samples: one launch each (prifit_mlp_chain_pool_f32), no
+    [P, C] tensor written, the pooled rows side by side in the level's output;
+  * SA3, the feature-propagation stacks and the head: one folded product per layer on prifit_gemm_f32 (bias, ReLU on load
+    through a unit-scale a_affine), then the existing pool / affine launch.
+No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
+to the live model: a shape the kernels do not take is an error."""
+import ctypes
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import nn_ops, ops, profiler
+from ._lib import call, cur_stream, ptr, query
+from .models import pointnet2_part_seg_msg as _msg
+from .models.pointnet_util import _col_index, _pad4
+
+_LL = ctypes.c_longlong
+_ALIGN = 64      # floats: every region of the flat buffer starts on a 256-byte boundary
+
+
+class _Folded:
+    """One (conv [+ BatchNorm]) layer's place in the flat buffer: W' [cout, ldw] at w_off, b' [cout] at b_off."""
+
+    def __init__(self, conv, bn):
+        self.conv, self.bn = conv, bn
+        self.cout = conv.weight.shape[0]
+        self.kin = conv.weight.numel() // self.cout
+        self.ldw = _pad4(self.kin)
+        self.w_off = self.b_off = -1
+        self.W = self.b = None                      # views of the flat buffer (FrozenPartSeg._bind)
+
+
+class _Packed:
+    """A column-packed copy of a folded first-layer weight: out [cout, len(cols)][c][j] = W'[c][cols[j]] (cols[j] < 0: 0)."""
+
+    def __init__(self, layer, cols):
+        self.layer, self.cols = layer, tuple(cols)
+        self.off = -1
+        self.W = None
+
+
+def _first_weight(layer, cols, packs):
+    """The folded weight of `layer` in the column order `cols`: the fold's own rows when that is what they are (the fold
+    pads a row with zero columns to a multiple of 4), else a packed copy."""
+    cols = tuple(cols)
+    if cols == tuple(range(layer.kin)) + (-1,) * (layer.ldw - layer.kin):
+        return layer
+    p = _Packed(layer, cols)
+    packs.append(p)
+    return p
+
+
+class FrozenPartSeg(nn.Module):
+    """The eval-mode forward of a `pointnet2_part_seg_msg.get_model` on folded weights; see the module docstring."""
+
+    def __init__(self, model):
+        super().__init__()
+        if not isinstance(model, _msg.get_model):
+            raise TypeError("freeze() takes a models.pointnet2_part_seg_msg.get_model (the SSG, cls, sem-seg and DGCNN networks "
+                            "have no frozen form), got %s" % type(model).__name__)
+        if model.reconstruct:
+            raise TypeError("freeze() takes a get_model with reconstruct=False: the AtlasNet decoder has no frozen form")
+        object.__setattr__(self, "_source", model)            # a reference, not a sub-module: its parameters are not ours
+        self.normal_channel = model.normal_channel
+        layers, packs = [], []
+
+        def stack(convs, bns):
+            out = [_Folded(c, b) for c, b in zip(convs, bns)]
+            layers.extend(out)
+            return out
+
+        # set abstraction, multi-scale: the first layer of a scale either straight from the upstream weight [C1, D + 3]
+        # (narrow inputs) or by linearity, U = [feat | xyz | 0] W^T per point and Vc = [c | 0] Wx^T per centre
+        self._sa = []
+        for sa in (model.sa1, model.sa2):
+            D = sa.conv_blocks[0][0].weight.shape[1] - 3
+            scales = []
+            for convs, bns in zip(sa.conv_blocks, sa.bn_blocks):
+                if len(convs) != 3:
+                    raise TypeError("freeze(): a set-abstraction scale with %d layers" % len(convs))
+                st = stack(convs, bns)
+                if D in (3, 6):
+                    first = (_first_weight(st[0], range(D + 3), packs),)
+                else:
+                    kp = _pad4(D + 3)
+                    first = (_first_weight(st[0], list(range(D + 3)) + [-1] * (kp - D - 3), packs),
+                             _first_weight(st[0], [D, D + 1, D + 2, -1], packs))
+                scales.append((st, first))
+            self._sa.append({"npoint": sa.npoint, "radii": list(sa.radius_list), "nsamples": list(sa.nsample_list), "D": D,
+                             "scales": scales})
+        # the group-all level: rows [xyz | feat | 0]
+        st = stack(model.sa3.mlp_convs, model.sa3.mlp_bns)
+        self._sa3 = (st, _first_weight(st[0], list(range(st[0].kin)) + [-1] * (st[0].ldw - st[0].kin), packs))
+        # feature propagation: rows [interpolated (D2) | points1 (D1) | 0], upstream concatenates [points1 | interpolated]
+        self._fp = {}
+        d2 = st[-1].cout
+        for name in ("fp3", "fp2", "fp1"):
+            fp = getattr(model, name)
+            st = stack(fp.mlp_convs, fp.mlp_bns)
+            d1 = st[0].kin - d2
+            kp = _pad4(d1 + d2)
+            cols = list(range(d1, d1 + d2)) + list(range(d1)) + [-1] * (kp - d1 - d2)
+            self._fp[name] = (st, _first_weight(st[0], cols, packs), d1, d2)
+            d2 = st[-1].cout
+        self._head = stack([model.conv1], [model.bn1])
+        self._conv2, self._emb = stack([model.conv2, model.extra_conv_emb], [None, None])
+        self._layers, self._packs = layers, packs
+        if len(layers) > query("prifit_fold_bn_max_jobs"):
+            raise TypeError("freeze(): %d layers, prifit_fold_bn takes %d" % (len(layers), query("prifit_fold_bn_max_jobs")))
+
+        # the flat buffer: [W' | b'] of every layer, the packed first-layer weights, then the unit affine (ones, zeros) that
+        # turns the product kernel's normalise-on-load into a plain ReLU
+        off = 0
+
+        def take(n):
+            nonlocal off
+            at, off = off, off + (n + _ALIGN - 1) // _ALIGN * _ALIGN
+            return at
+
+        for ly in layers:
+            ly.w_off, ly.b_off = take(ly.cout * ly.ldw), take(ly.cout)
+        for p in packs:
+            p.off = take(p.layer.cout * len(p.cols))
+        self._unit_c = max(ly.cout for ly in layers)
+        self._ones_off, self._zeros_off = take(self._unit_c), take(self._unit_c)
+        dev = model.conv1.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("freeze() needs the model on the GPU (HIP backend only, no CPU path)")
+        flat = torch.empty(off, dtype=torch.float32, device=dev)
+        flat[self._ones_off:self._ones_off + self._unit_c] = 1.0
+        flat[self._zeros_off:self._zeros_off + self._unit_c] = 0.0
+        self.flat = nn.Parameter(flat, requires_grad=False)
+        self._bound = None
+        nn.Module.train(self, False)
+        self.refresh()
+
+    # ------------------------------------------------------------------ module protocol
+    def train(self, mode=True):
+        if mode:
+            raise RuntimeError("FrozenPartSeg is an inference module: train the live model and call refresh()")
+        return nn.Module.train(self, False)
+
+    def _bind(self):
+        """Views of the flat buffer for every consumer (again after the module moved: `.to()` replaces the parameter's storage)."""
+        flat = self.flat.data
+        if self._bound == (flat.data_ptr(), flat.device):
+            return flat
+        for ly in self._layers:
+            ly.W = flat[ly.w_off:ly.w_off + ly.cout * ly.ldw].view(ly.cout, ly.ldw)
+            ly.b = flat[ly.b_off:ly.b_off + ly.cout]
+        for p in self._packs:
+            p.W = flat[p.off:p.off + p.layer.cout * len(p.cols)].view(p.layer.cout, len(p.cols))
+        self._ones = flat[self._ones_off:self._ones_off + self._unit_c]
+        self._zeros = flat[self._zeros_off:self._zeros_off + self._unit_c]
+        self._bound = (flat.data_ptr(), flat.device)
+        return flat
+
+    @torch.no_grad()
+    def refresh(self):
+        """Fold the live model's current weights and statistics into the flat buffer: one fold launch for every layer, one
+        pack launch for the column-permuted first-layer weights."""
+        flat = self._bind()
+        ls = self._layers
+        n = len(ls)
+        keep = []                                              # contiguous copies, alive until the launch is enqueued
+
+        def dp(t):
+            if t is None:
+                return None
+            if t.device != flat.device:
+                raise RuntimeError("refresh(): the live model is on %s, the frozen one on %s" % (t.device, flat.device))
+            t = t.detach()
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                t = t.float().contiguous()
+                keep.append(t)
+            return t.data_ptr()
+
+        arr = lambda vals: (ctypes.c_void_p * n)(*vals)
+        bn = lambda ly, name: None if ly.bn is None else getattr(ly.bn, name)
+        call("prifit_fold_bn", n, arr([dp(ly.conv.weight) for ly in ls]), (ctypes.c_int32 * n)(*[ly.cout for ly in ls]),
+             (ctypes.c_int32 * n)(*[ly.kin for ly in ls]), arr([dp(ly.conv.bias) for ly in ls]),
+             arr([dp(bn(ly, "weight")) for ly in ls]), arr([dp(bn(ly, "bias")) for ly in ls]),
+             arr([dp(bn(ly, "running_mean")) for ly in ls]), arr([dp(bn(ly, "running_var")) for ly in ls]),
+             (ctypes.c_float * n)(*[0.0 if ly.bn is None else float(ly.bn.eps) for ly in ls]),
+             (ctypes.c_longlong * n)(*[ly.w_off for ly in ls]), (ctypes.c_int32 * n)(*[ly.ldw for ly in ls]),
+             (ctypes.c_longlong * n)(*[ly.b_off for ly in ls]), ptr(flat), _LL(flat.numel()), cur_stream())
+        most = query("prifit_pack_cols_max_jobs")
+        for lo in range(0, len(self._packs), most):
+            ps = self._packs[lo:lo + most]
+            m = len(ps)
+            maps = [_col_index(p.cols, p.layer.ldw, flat.device)[0] for p in ps]
+            call("prifit_pack_cols_multi", m, nn_ops._ptr_array([p.layer.W for p in ps]),
+                 (ctypes.c_int32 * m)(*[p.layer.cout for p in ps]), (ctypes.c_int32 * m)(*[p.layer.ldw for p in ps]),
+                 nn_ops._ptr_array(maps), (ctypes.c_int32 * m)(*[len(p.cols) for p in ps]), nn_ops._ptr_array([p.W for p in ps]),
+                 cur_stream())
+        return self
+
+    # ------------------------------------------------------------------ the forward
+    def forward(self, xyz, cls_label, fps_start=None, include_convex_loss=False, embed=False, **ignored_forward_kwargs):
+        """xyz [B, C, N] (C = 6 with normals), cls_label [B, 1, 16] or [B, 16] one-hot -> the live model's eval-mode 5-tuple
+        (seg [B,N,parts], (l1 [B,128,512], l2 [B,256,128], l3 [B,1024,1]), feat [B,128,N], zeros(1), zeros(1)); embed=True
+        appends (None, None, feat_embed [B,128,N]) like the live model.  The other forward keywords of the live model
+        (evaluation=..., quantile=..., ...) steer the fit path only and are ignored."""
+        if include_convex_loss:
+            raise ValueError("FrozenPartSeg has no fit path: include_convex_loss=True belongs to the live model")
+        with torch.no_grad():
+            return self._forward(xyz, cls_label, fps_start, embed)
+
+    def predict(self, xyz, cls_label, fps_start=None):
+        return self.forward(xyz, cls_label, fps_start)[0]
+
+    def _forward(self, xyz, cls_label, fps_start, embed):
+        self._bind()
+        B, _, N = xyz.shape
+        pts = xyz.permute(0, 2, 1).contiguous().float()
+        l0_xyz = pts[:, :, :3].contiguous() if self.normal_channel else pts
+        s1, s2 = fps_start if fps_start is not None else (None, None)
+        l1_xyz, l1_points = self._sa_level(self._sa[0], l0_xyz, pts, s1)
+        l2_xyz, l2_points = self._sa_level(self._sa[1], l1_xyz, l1_points, s2)
+        # SA3 (group all): rows [xyz | feat | 0], three products, max over the cloud's points
+        st, w0 = self._sa3
+        S2 = l2_xyz.shape[1]
+        rows = self._rows([l2_xyz, l2_points], B, S2, w0.W.shape[1])
+        l3_points = torch.empty(B, st[-1].cout, dtype=torch.float32, device=pts.device)
+        self._stack(rows, False, st, w0.W, S2, l3_points)
+        l3_points = l3_points.reshape(B, 1, -1)
+        l3_xyz = None                                                        # one centre per cloud: nothing to interpolate between
+        l2_up = self._fp_level("fp3", l2_xyz, l3_xyz, l2_points, l3_points)
+        l1_up = self._fp_level("fp2", l1_xyz, l2_xyz, l1_points, l2_up)
+        onehot = cls_label.reshape(B, 1, 16).expand(B, N, 16).to(pts.dtype)
+        skip = torch.cat([onehot, l0_xyz, pts], dim=-1)
+        l0_up = self._fp_level("fp1", l0_xyz, l1_xyz, skip, l1_up)
+        feat = torch.empty(B * N, self._head[0].cout, dtype=torch.float32, device=pts.device)
+        self._stack(l0_up.reshape(B * N, -1), False, self._head, self._head[0].W, 0, feat)
+        seg = F.log_softmax(self._linear(feat, self._conv2), dim=1).reshape(B, N, -1)
+        zero = torch.zeros(2, device=pts.device)
+        outs = (seg, (l1_up.permute(0, 2, 1), l2_up.permute(0, 2, 1), l3_points.permute(0, 2, 1)),
+                feat.reshape(B, N, -1).permute(0, 2, 1), zero[:1], zero[1:])
+        if embed:
+            outs += (None, None, self._linear(feat, self._emb).reshape(B, N, -1).permute(0, 2, 1))
+        return outs
+
+    def _rows(self, parts, B, n, kp):
+        """[B n, kp] rows = the parts side by side, zero padded (the zeros are the flat buffer's: no fill launch)."""
+        have = sum(p.shape[-1] for p in parts)
+        if kp > have:
+            parts = parts + [self._zeros[:kp - have].expand(B, n, kp - have)]
+        return torch.cat(parts, dim=-1).reshape(B * n, kp)
+
+    def _linear(self, x, ly):
+        P = x.shape[0]
+        y = torch.empty(P, ly.cout, dtype=torch.float32, device=x.device)
+        nn_ops.gemm(nn_ops.NT, P, ly.cout, ly.kin, x, x.stride(0), ly.W, ly.ldw, y, ly.cout, bias=ly.b)
+        return y
+
+    def _stack(self, x, preact, layers, w0, pool_K, out):
+        """relu(W' . + b') layer after layer on the product kernel, then the max over each pool_K rows (0: none) into
+        `out` ([G, C] column window or [P, C]).  preact: x already is layer 0's pre-activation.  The ReLU of a layer is
+        applied when the next product loads it (a_affine with unit scale) and by the pool / affine launch at the end."""
+        P = x.shape[0]
+        unit = None
+        for l, ly in enumerate(layers):
+            if l == 0 and preact:
+                y = x
+            else:
+                W = w0 if l == 0 else ly.W
+                Kin = W.shape[1] if l == 0 else ly.kin
+                y = torch.empty(P, ly.cout, dtype=torch.float32, device=x.device)
+                nn_ops.gemm(nn_ops.NT, P, ly.cout, Kin, x, x.stride(0), W, W.stride(0), y, ly.cout, a_affine=unit, bias=ly.b)
+            x, unit = y, (self._ones, self._zeros)
+        C = x.shape[1]
+        if pool_K:
+            G = P // pool_K
+            arg = torch.empty(G, C, dtype=torch.int32, device=x.device)     # the pool launch's required output; never read
+            call("prifit_pool_fwd", ptr(x), _LL(x.stride(0)), ptr(self._ones), ptr(self._zeros), G, pool_K, C, 0, ctypes.c_float(0.0),
+                 ptr(out), _LL(out.stride(0)), ptr(arg), cur_stream())
+        else:
+            call("prifit_affine_relu", ptr(x), _LL(x.stride(0)), ptr(self._ones), ptr(self._zeros), P, C, 0, ctypes.c_float(0.0),
+                 ptr(out), _LL(out.stride(0)), cur_stream())
+
+    def _sa_level(self, lv, xyz, feats, fps_start):
+        """One multi-scale set-abstraction level: xyz [B,N,3], feats [B,N,D] -> (new_xyz [B,S,3], out [B,S,sum C2])."""
+        B, N, _ = xyz.shape
+        S, radii, nsamples, D = lv["npoint"], lv["radii"], lv["nsamples"], lv["D"]
+        scales = lv["scales"]
+        R = len(scales)
+        widths = [st[0].cout for st, _ in scales]
+        if feats.shape[-1] != D:
+            raise ValueError("FrozenPartSeg: %d point channels, the frozen model takes %d" % (feats.shape[-1], D))
+        if not nn_ops.sa_group_supported(N, nsamples, widths):
+            raise NotImplementedError("FrozenPartSeg: clouds of %d points are outside prifit_sa_group_linear_fwd (N <= 2048)" % N)
+        _, new_xyz = ops.farthest_point_sample(xyz, S, fps_start, return_xyz=True)
+        dev = xyz.device
+        bs = [st[0].b for st, _ in scales]
+        Ws = Us = Vcs = None
+        direct = len(scales[0][1]) == 1
+        if direct:
+            Ws = [first[0].W for _, first in scales]
+        else:
+            kp = scales[0][1][0].W.shape[1]
+            rows = self._rows([feats, xyz], B, N, kp)
+            c4 = self._rows([new_xyz], B, S, 4)
+            Us, Vcs = [], []
+            for (st, (w_pt, w_c)), C1 in zip(scales, widths):
+                U = torch.empty(B * N, C1, dtype=torch.float32, device=dev)
+                Vc = torch.empty(B * S, C1, dtype=torch.float32, device=dev)
+                nn_ops.gemm(nn_ops.NT, B * N, C1, kp, rows, kp, w_pt.W, kp, U, C1)
+                nn_ops.gemm(nn_ops.NT, B * S, C1, 4, c4, 4, w_c.W, 4, Vc, C1)
+                Us.append(U)
+                Vcs.append(Vc)
+        Ys = [torch.empty(B * S * k, c, dtype=torch.float32, device=dev) for k, c in zip(nsamples, widths)]
+        idxs = [torch.empty(B, S, k, dtype=torch.int32, device=dev) for k in nsamples]
+        pa = nn_ops._ptr_array
+        with profiler.span("sa_group_linear"):
+            call("prifit_sa_group_linear_fwd", ptr(xyz), ptr(new_xyz), B, N, S, R,
+                 (ctypes.c_float * R)(*[float(np.float32(r ** 2)) for r in radii]), (ctypes.c_int * R)(*[int(k) for k in nsamples]),
+                 (ctypes.c_int * R)(*widths), 0 if direct else 1, ptr(feats) if direct else None, D if direct else 0, 1,
+                 int(direct and D == 3 and feats.data_ptr() == xyz.data_ptr()), pa(Ws) if direct else None, None if direct else pa(Us),
+                 None if direct else pa(Vcs), pa(bs), pa(Ys), pa([None] * R), pa(idxs), cur_stream())
+        outw = [st[-1].cout for st, _ in scales]
+        wide = torch.empty(B * S, sum(outw), dtype=torch.float32, device=dev)
+        c0 = 0
+        for (st, _), K, Y, C2 in zip(scales, nsamples, Ys, outw):
+            win = wide[:, c0:c0 + C2]
+            c0 += C2
+            C0, C1 = st[0].cout, st[1].cout
+            if query("prifit_mlp_chain_pool_supported", C0, C1, C2, K):
+                G = B * S
+                nws = query("prifit_mlp_chain_pool_workspace", G, K, C0, C1, C2)
+                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
+                with profiler.span(profiler.tag("mlp_chain_pool", G * K, C0, C1, C2), 2.0 * G * K * (C0 * C1 + C1 * C2)):
+                    call("prifit_mlp_chain_pool_f32", ptr(Y), _LL(C0), G, K, C0, C1, C2, ptr(st[1].W), _LL(st[1].ldw), ptr(st[1].b),
+                         ptr(st[2].W), _LL(st[2].ldw), ptr(st[2].b), ptr(win), _LL(wide.stride(0)), ptr(ws), cur_stream())
+            else:
+                self._stack(Y, True, st, None, K, win)
+        return new_xyz, wide.reshape(B, S, -1)
+
+    def _fp_level(self, name, xyz1, xyz2, points1, points2):
+        """Feature propagation: xyz1 [B,N,3], xyz2 [B,S,3] (None: S == 1), points1 [B,N,D1], points2 [B,S,D2] -> [B,N,C]."""
+        st, w0, D1, D2 = self._fp[name]
+        B, N, _ = xyz1.shape
+        S = points2.shape[1]
+        kp = w0.W.shape[1]
+        idx = w = None
+        if S > 1:
+            idx, w = ops.three_nn(xyz1, xyz2)
+        points1, points2 = points1.contiguous(), points2.contiguous()
+        rows = torch.empty(B * N, kp, dtype=torch.float32, device=xyz1.device)
+        call("prifit_fp_rows", ptr(points2), ptr(idx), ptr(w), ptr(points1), B, N, S, D2, D1, kp, ptr(rows), cur_stream())
+        out = torch.empty(B * N, st[-1].cout, dtype=torch.float32, device=xyz1.device)
+        self._stack(rows, False, st, w0.W, 0, out)
+        return out.reshape(B, N, -1)
+
+
+def freeze(model):
+    """A FrozenPartSeg of `model` (a models.pointnet2_part_seg_msg.get_model on the GPU, reconstruct=False); TypeError for
+    every other network."""
+    return FrozenPartSeg(model)

@@ -1,0 +1,119 @@
+"""The eval-mode forward of the MSG part-segmentation network at the benchmark shape (B = 24 clouds of N = 2048 points), by
+HIP events: (a) the live model in .eval() under no_grad -- the route evaluate_loader has always run -- against (b) the frozen
+model of prifit_amd.inference on the same weights, inputs and sampling starts; then, per SA1 / SA2 scale, the chain kernel
+(prifit_mlp_chain_pool_f32) against the launches it replaces (SharedMLPFn in eval mode on the same first-layer rows: the
+coefficient arithmetic, two products, the pool).  Every arm sees the same seeded state in every repeat; the arms alternate
+within a round (the box is shared) and the table gives the median and the (min .. max) of the rounds.  The outputs of the two
+arms are compared before anything is timed.
+usage (GPU box): python tools/bench_infer.py [repetitions, default 20] [rounds, default 5] [output file, default profiles/infer.txt]"""
+import os, sys
+import numpy as np, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from prifit_amd import inference
+from prifit_amd._lib import call, cur_stream, ptr, query
+from prifit_amd.models import pointnet2_part_seg_msg as M
+from prifit_amd.nn_ops import FrontEnd, SharedMLPFn
+
+B, N = 24, 2048
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "infer.txt")
+dev = torch.device("cuda", 0)
+
+
+def timed(step, warm, reps):
+    for _ in range(warm): step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps): step()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def alternate(steps, warm, reps, rounds):
+    """-> per step (median, min, max) ms over `rounds` rounds, the steps taking turns inside every round."""
+    got = [[] for _ in steps]
+    for _ in range(rounds):
+        for i, s in enumerate(steps):
+            got[i].append(timed(s, warm, reps))
+    return [(float(np.median(g)), min(g), max(g)) for g in got]
+
+
+torch.manual_seed(0)
+net = M.get_model(50).to(dev)
+with torch.no_grad():
+    for m in net.modules():
+        if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d)):
+            m.weight.uniform_(0.5, 1.5); m.bias.normal_(0.0, 0.1)
+    net.train()
+    for _ in range(2):
+        net(torch.rand(4, 3, N, device=dev) * 2 - 1, torch.eye(16, device=dev)[torch.randint(0, 16, (4,))].reshape(4, 1, 16))
+net.eval()
+frozen = inference.freeze(net)
+g = torch.Generator().manual_seed(1)
+xyz = (torch.rand(B, 3, N, generator=g) * 2 - 1).to(dev)
+onehot = torch.eye(16)[torch.randint(0, 16, (B,), generator=g)].reshape(B, 1, 16).to(dev)
+start = (torch.randint(0, N, (B,), generator=g).to(dev), torch.randint(0, 512, (B,), generator=g).to(dev))
+
+
+def live():
+    with torch.no_grad():
+        return net(xyz, onehot, fps_start=start)
+
+
+def cold():
+    return frozen(xyz, onehot, fps_start=start)
+
+
+a, b = live(), cold()
+torch.cuda.synchronize()
+d_seg, d_feat = float((a[0] - b[0]).abs().max()), float((a[2] - b[2]).abs().max())
+same = float((a[0].argmax(-1) == b[0].argmax(-1)).float().mean())
+lines = ["eval-mode forward, B = %d x N = %d, %d repetitions x %d alternating rounds (median, min .. max), %s"
+         % (B, N, reps, rounds, torch.cuda.get_device_name(0)),
+         "outputs: max |seg_live - seg_frozen| = %.3g, max |feat_live - feat_frozen| = %.3g, arg-max equal on %.4f %% of the points"
+         % (d_seg, d_feat, 100.0 * same)]
+(l_ms, l_lo, l_hi), (f_ms, f_lo, f_hi) = alternate([live, cold], 3, reps, rounds)
+lines += ["(a) live model.eval(), no_grad   %8.3f ms  (%.3f .. %.3f)" % (l_ms, l_lo, l_hi),
+          "(b) frozen                       %8.3f ms  (%.3f .. %.3f)" % (f_ms, f_lo, f_hi),
+          "ratio live / frozen              %8.2fx%s" % (l_ms / f_ms, "" if f_ms <= l_ms else "  (frozen NOT faster)"),
+          "", "per scale: layers 2 + 3 + pool of one set-abstraction scale on its first-layer rows",
+          "  scale (C0, C1, C2, K)        rows      replaced launches ms        chain kernel ms      ratio   share of the fp32 MFMA peak"]
+
+for lv in frozen._sa:
+    S = lv["npoint"]
+    for (st, _), K in zip(lv["scales"], lv["nsamples"]):
+        C0, C1, C2 = st[0].cout, st[1].cout, st[2].cout
+        G = B * S
+        P = G * K
+        X = torch.randn(P, C0, device=dev)
+        out = torch.empty(G, C2, device=dev)
+        ts = [None, None] + [getattr(st[0].bn, k) for k in ("weight", "bias", "running_mean", "running_var")]
+        for ly in st[1:]:
+            ts += [ly.conv.weight.reshape(ly.cout, -1), ly.conv.bias] + [getattr(ly.bn, k) for k in ("weight", "bias", "running_mean", "running_var")]
+
+        def replaced():
+            cfg = {"pool_K": K, "training": False, "eps": st[0].bn.eps, "momentum": [0.1] * 3, "front": FrontEnd("preact", True),
+                   "pool_out": out}
+            with torch.no_grad():
+                SharedMLPFn.apply(X, cfg, *ts)
+
+        def chain():
+            call("prifit_mlp_chain_pool_f32", ptr(X), C0, G, K, C0, C1, C2, ptr(st[1].W), st[1].ldw, ptr(st[1].b), ptr(st[2].W),
+                 st[2].ldw, ptr(st[2].b), ptr(out), C2, None, cur_stream())
+
+        taken = bool(query("prifit_mlp_chain_pool_supported", C0, C1, C2, K))
+        if not taken:
+            lines.append("  (%3d, %3d, %3d, %3d)  %9d   not taken by the chain kernel: the folded products serve it" % (C0, C1, C2, K, P))
+            continue
+        (r_ms, r_lo, r_hi), (c_ms, c_lo, c_hi) = alternate([replaced, chain], 3, reps, rounds)
+        peak = 2.0 * P * (C0 * C1 + C1 * C2) / (c_ms * 1e-3) / 157.3e12
+        lines.append("  (%3d, %3d, %3d, %3d)  %9d   %7.3f (%.3f .. %.3f)   %7.3f (%.3f .. %.3f)   %5.2fx   %4.1f %%%s"
+                     % (C0, C1, C2, K, P, r_ms, r_lo, r_hi, c_ms, c_lo, c_hi, r_ms / c_ms, 100.0 * peak,
+                        "" if c_ms <= r_hi else "  (chain NOT faster)"))
+print("\n".join(lines))
+os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+with open(out_path, "w") as f:
+    f.write("\n".join(lines) + "\n")
