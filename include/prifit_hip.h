@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 800
+#define PRIFIT_ABI_VERSION 801
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1050,6 +1050,32 @@ long long prifit_mlp_chain_pool_workspace(int G, int pool_K, int C0, int C1, int
 int prifit_mlp_chain_pool_f32(const float *X, long long ldx, int G, int pool_K, int C0, int C1, int C2, const float *W1,
                               long long ldw1, const float *b1, const float *W2, long long ldw2, const float *b2, float *out,
                               long long ldo, float *workspace, void *stream);
+
+/* The per-point tail of the part-segmentation network in one launch, on folded weights: fp1's two layers, conv1 + bn1 and
+ * conv2 (models/pointnet2_part_seg_msg.py:86-133 in eval mode, dropout off), ending in the scores and / or in the
+ * category-restricted arg-max of testing.py:141-144.  X [P, ldx] are RAW rows (no ReLU on load), K0 wide; for l = 1 .. L:
+ * z_l = W_l a_(l-1) + b_l, a_l = relu(z_l) after every layer but the last (a NaN stays a NaN).  W, ldw, b: HOST arrays of L
+ * entries, read before the call returns; W_l [widths[l-1], ldw_l] and b_l as prifit_fold_bn writes them.
+ *   scores [P, lds] or NULL: z_L[0 : C_L], columns C_L .. lds - 1 are not written;
+ *   labels [P] int32 or NULL: the FIRST index of the maximum of z_L among the allowed channels, -1 where none is allowed.
+ *     Channel c is allowed for row p iff cat_of_label[c] == shape_cat[p / rows_per_shape] (cat_of_label [C_L] int32 as
+ *     prifit_seg_metrics takes it, shape_cat [P / rows_per_shape] int32, both on the device; a negative shape_cat is no
+ *     category: -1 for its rows, as prifit_seg_metrics answers); both NULL: every channel is allowed.  The order is prifit_seg_metrics' (numpy's), bit for bit: a NaN beats every number and the first NaN wins,
+ *     -0 == +0, a row whose allowed scores are all -inf gives the first allowed channel.
+ * No [P, 128] tensor is written: a wave keeps its 32 rows in registers from the load to the arg-max (v_mfma_f32_32x32x2_f32,
+ * fp32 accumulation), the lane that holds a row's channels ranks them and meets the other half-wave's lane once.
+ * prifit_mlp_chain_rows_supported: 1 for L == 4, widths (128, 128, 128, C_L) with 1 <= C_L <= 64, K0 % 8 == 0 and
+ * 8 <= K0 <= 160 (152 = [interpolated 128 | one-hot 16 | xyz 3 | xyz 3 | 0 0], 160 the same with normals); 0 otherwise.
+ * prifit_mlp_chain_rows_workspace: floats of `workspace` the call needs (0 today: workspace may be NULL).  Any P >= 1.
+ * PRIFIT_EINVAL without a launch: an unsupported shape; scores and labels both NULL; X, a W_l or a b_l NULL or not 16-byte
+ * aligned; ldx < K0, ldw_l < the layer's input width, either not a multiple of 4; lds < C_L; P < 1 or > 2^31 - 1;
+ * rows_per_shape <= 0; with labels: only one of cat_of_label / shape_cat given, or both and P % rows_per_shape != 0. */
+int prifit_mlp_chain_rows_supported(int K0, int L, const int32_t *widths);
+long long prifit_mlp_chain_rows_workspace(long long P, int K0, int L, const int32_t *widths);
+int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                              const float *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
+                              int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
+                              float *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
 //
 //   fold_bn_kernel         every layer of a network in ONE launch: W' = W * s, b' = (b - mean) * s + beta, s = gamma / sqrt(var + eps)
 //   mlp_chain_pool_kernel  layers 2 and 3 of a scale and its pool in one launch, the intermediates in registers
+//   mlp_chain_rows_kernel  the per-point tail (fp1, conv1 + bn1, conv2) and the restricted arg-max in one launch
 //
 // The chain kernel computes the TRANSPOSED products on v_mfma_f32_32x32x2_f32 (exact fp32, the instruction of gemm.hip and
 // gemm_stream.hip): H^T = W1' X^T and Y^T = W2' H^T, the weights as the A operand and 32 rows of the activation as the B
@@ -219,6 +220,198 @@ int chain_shape(int C0, int C1, int C2)
 
 bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
 
+// ---- the per-point tail of the part-segmentation network: four layers over raw rows, scores and / or part labels out
+//
+// The layout argument above does not stop at two layers: whatever the depth, the C/D registers of one transposed product
+// are the B operand of the next, as long as the next weight is read at columns 32b + 8g + 4h + m.  So a wave carries its 32
+// rows through fp1's two layers, conv1 + bn1 and conv2 in registers; the last product's C/D layout leaves lane (j, h) with
+// the scores of channels 32b + 8g + 4h + m of row j, which it ranks itself before one exchange with lane j of the other half.
+constexpr int ROWS_L = 4, ROWS_W = 128, ROWS_NB = ROWS_W / 32, ROWS_MAX_CL = 64, ROWS_MAX_K0 = 160;
+
+struct RowsArgs {
+    const float *X;
+    long long ldx, P;
+    const float *W[ROWS_L], *b[ROWS_L];
+    long long ldw[ROWS_L];
+    int CL;
+    float *scores;
+    long long lds;
+    int32_t *labels;
+    const int32_t *cat_of_label, *shape_cat;     // shape_cat NULL: every channel < CL is allowed
+    int N;                                       // rows per shape
+};
+
+// ReLU that keeps a NaN (np.maximum, torch.relu): a NaN input row reaches the scores, where the arg-max rule ranks it
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+
+// order-preserving key of a score among the ALLOWED channels: score_key of seg_metrics.hip, bit for bit (NaN = the largest
+// key, -0 = +0, always >= 0x007fffff so that 0 is free for the channels outside the window)
+__device__ __forceinline__ unsigned rows_score_key(float x)
+{
+    const unsigned u = __float_as_uint(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if ((u << 1) == 0) return 0x80000000u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// one 128 -> 128 layer on the registers: out = relu(W in + bias), both in the C/D layout (block b, register 4g + m of lane
+// (j, h) = channel 32b + 8g + 4h + m of row j)
+__device__ __forceinline__ void rows_layer(const float *__restrict__ W, long long ldw, const float *__restrict__ bias,
+                                           const f32x16 (&in)[ROWS_NB], f32x16 (&out)[ROWS_NB], int li, int lh)
+{
+#pragma unroll
+    for (int b2 = 0; b2 < ROWS_NB; ++b2) {
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const float *wr = W + (long long)(32 * b2 + li) * ldw + 4 * lh;
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const float4 a = ld4(wr + 32 * b + 8 * gq);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in[b][4 * gq + 0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in[b][4 * gq + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in[b][4 * gq + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in[b][4 * gq + 3], acc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const float4 bb = ld4(bias + 32 * b2 + 8 * gq + 4 * lh);
+            acc[4 * gq + 0] = relu_nan(acc[4 * gq + 0] + bb.x);
+            acc[4 * gq + 1] = relu_nan(acc[4 * gq + 1] + bb.y);
+            acc[4 * gq + 2] = relu_nan(acc[4 * gq + 2] + bb.z);
+            acc[4 * gq + 3] = relu_nan(acc[4 * gq + 3] + bb.w);
+        }
+        out[b2] = acc;
+    }
+}
+
+// X [P, 8 KQ] raw rows -> z = W4 relu(W3 relu(W2 relu(W1 x + b1) + b2) + b3) + b4, widths (128, 128, 128, CL <= 64);
+// scores[p][0:CL] = z and / or labels[p] = the first maximum of z among the allowed channels (-1: none allowed)
+template <int KQ>
+__global__ __launch_bounds__(256) void mlp_chain_rows_kernel(const RowsArgs g)
+{
+    __shared__ int s_cat[ROWS_MAX_CL];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int li = lane & 31, lh = lane >> 5;
+    const int CL = g.CL;
+    if (g.labels && g.shape_cat) {                // (grid-uniform) the category table, once per workgroup
+        if (threadIdx.x < ROWS_MAX_CL) s_cat[threadIdx.x] = threadIdx.x < CL ? g.cat_of_label[threadIdx.x] : 0;
+        __syncthreads();                          // the only barrier, before the chain starts
+    }
+    const long long row0 = (long long)blockIdx.x * CHAIN_ROWS + 32 * wave;
+    if (row0 >= g.P) return;                      // wave-uniform
+    const long long row = row0 + li;
+    const bool live = row < g.P;                  // a row past the end computes on a copy of the last row and stores nothing
+    const long long rowc = live ? row : g.P - 1;
+
+    f32x16 ha[ROWS_NB], hb[ROWS_NB];
+    {
+        // B operand of layer 1: lane (j, h) holds X[row0 + j][8q + 4h + 0..3]
+        float4 xf[KQ];
+        const float *xr = g.X + rowc * g.ldx + 4 * lh;
+#pragma unroll
+        for (int q = 0; q < KQ; ++q) xf[q] = ld4(xr + 8 * q);
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {
+            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const float *wr = g.W[0] + (long long)(32 * b + li) * g.ldw[0] + 4 * lh;
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) {
+                const float4 a = ld4(wr + 8 * q);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xf[q].x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xf[q].y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xf[q].z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xf[q].w, acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const float4 bb = ld4(g.b[0] + 32 * b + 8 * gq + 4 * lh);
+                acc[4 * gq + 0] = relu_nan(acc[4 * gq + 0] + bb.x);
+                acc[4 * gq + 1] = relu_nan(acc[4 * gq + 1] + bb.y);
+                acc[4 * gq + 2] = relu_nan(acc[4 * gq + 2] + bb.z);
+                acc[4 * gq + 3] = relu_nan(acc[4 * gq + 3] + bb.w);
+            }
+            ha[b] = acc;
+        }
+    }
+    rows_layer(g.W[1], g.ldw[1], g.b[1], ha, hb, li, lh);
+    rows_layer(g.W[2], g.ldw[2], g.b[2], hb, ha, li, lh);
+
+    // layer 4, no ReLU: channels >= CL are zero A rows (the row index clamped for the load, the value zeroed)
+    const bool vec = g.scores && !(g.lds & 3) && !((uintptr_t)g.scores & 15);      // grid-uniform: float4 stores are aligned
+    const int cat = (g.labels && g.shape_cat) ? g.shape_cat[(int)rowc / g.N] : 0;      // P <= 2^31 - 1
+    unsigned long long best = 0;                  // (key << 32) | (63 - channel): the larger key, then the lower channel
+#pragma unroll
+    for (int b2 = 0; b2 < ROWS_MAX_CL / 32; ++b2) {
+        if (32 * b2 >= CL) break;                 // grid-uniform
+        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        const int c = 32 * b2 + li;
+        const bool ok = c < CL;
+        const float *wr = g.W[3] + (long long)(ok ? c : 0) * g.ldw[3] + 4 * lh;
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                float4 a = ld4(wr + 32 * b + 8 * gq);
+                if (!ok) a = make_float4(0.f, 0.f, 0.f, 0.f);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, ha[b][4 * gq + 0], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, ha[b][4 * gq + 1], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, ha[b][4 * gq + 2], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, ha[b][4 * gq + 3], acc, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+            const int c0 = 32 * b2 + 8 * gq + 4 * lh;
+            float z[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) z[m] = acc[4 * gq + m] + (c0 + m < CL ? g.b[3][c0 + m] : 0.f);
+            if (g.scores && live) {
+                float *sr = g.scores + row * g.lds + c0;
+                if (vec && c0 + 4 <= CL) *reinterpret_cast<float4 *>(sr) = make_float4(z[0], z[1], z[2], z[3]);
+                else {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+                        if (c0 + m < CL) sr[m] = z[m];
+                }
+            }
+            if (g.labels) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {     // ascending channels within the lane: > keeps the first maximum
+                    const int ch = c0 + m;
+                    // a negative category is none (prifit_seg_metrics' shape_cat -1), whatever cat_of_label holds
+                    const bool allowed = ch < CL && (!g.shape_cat || (cat >= 0 && s_cat[ch < ROWS_MAX_CL ? ch : 0] == cat));
+                    const unsigned long long k =
+                        allowed ? ((unsigned long long)rows_score_key(z[m]) << 32) | (unsigned)(63 - ch) : 0ull;
+                    best = k > best ? k : best;
+                }
+            }
+        }
+    }
+    if (g.labels) {
+        // lanes j and j + 32 hold the two halves of row j's channels: one exchange, the tie goes to the lower channel
+        const unsigned hi = __shfl_xor((unsigned)(best >> 32), 32), lo = __shfl_xor((unsigned)best, 32);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        best = other > best ? other : best;
+        if (lh == 0 && live) g.labels[row] = (best >> 32) ? 63 - (int)(best & 63u) : -1;
+    }
+}
+
+template <int KQ>
+void rows_launch(const RowsArgs &g, hipStream_t st)
+{
+    const unsigned grid = (unsigned)((g.P + CHAIN_ROWS - 1) / CHAIN_ROWS);
+    hipLaunchKernelGGL((mlp_chain_rows_kernel<KQ>), dim3(grid), dim3(256), 0, st, g);
+}
+
+template <int KQ>
+void rows_dispatch(int kq, const RowsArgs &g, hipStream_t st)
+{
+    if (kq == KQ) rows_launch<KQ>(g, st);
+    else if constexpr (KQ > 1) rows_dispatch<KQ - 1>(kq, g, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -282,6 +475,45 @@ int prifit_mlp_chain_pool_f32(const float *X, long long ldx, int G, int pool_K, 
     case 3: chain_launch<128, 128, 256>(g, st); break;
     default: chain_launch<128, 196, 256>(g, st); break;
     }
+    return prifit_check_launch();
+}
+
+int prifit_mlp_chain_rows_supported(int K0, int L, const int32_t *widths)
+{
+    if (L != ROWS_L || !widths || K0 < 8 || K0 > ROWS_MAX_K0 || (K0 & 7)) return 0;
+    for (int l = 0; l + 1 < ROWS_L; ++l)
+        if (widths[l] != ROWS_W) return 0;
+    return (widths[ROWS_L - 1] >= 1 && widths[ROWS_L - 1] <= ROWS_MAX_CL) ? 1 : 0;
+}
+
+long long prifit_mlp_chain_rows_workspace(long long P, int K0, int L, const int32_t *widths)
+{
+    (void)P; (void)K0; (void)L; (void)widths;
+    return 0;   // the intermediates live in registers
+}
+
+int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                              const float *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
+                              int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
+                              float *workspace, void *stream)
+{
+    (void)workspace;
+    if (!prifit_mlp_chain_rows_supported(K0, L, widths) || !X || !W || !ldw || !b || (!scores && !labels) || P < 1 ||
+        P > 0x7fffffffLL || ldx < K0 || (ldx & 3) || mis16(X) || rows_per_shape <= 0)
+        return PRIFIT_EINVAL;
+    const int CL = widths[ROWS_L - 1];
+    if (scores && lds < CL) return PRIFIT_EINVAL;
+    if (labels && (shape_cat != nullptr) != (cat_of_label != nullptr)) return PRIFIT_EINVAL;
+    if (labels && shape_cat && P % rows_per_shape) return PRIFIT_EINVAL;
+    RowsArgs g = {};
+    for (int l = 0; l < ROWS_L; ++l) {
+        const int kin = l ? ROWS_W : K0;
+        if (!W[l] || !b[l] || ldw[l] < kin || (ldw[l] & 3) || mis16(W[l]) || mis16(b[l])) return PRIFIT_EINVAL;
+        g.W[l] = W[l]; g.b[l] = b[l]; g.ldw[l] = ldw[l];
+    }
+    g.X = X; g.ldx = ldx; g.P = P; g.CL = CL; g.scores = scores; g.lds = lds; g.labels = labels;
+    g.cat_of_label = labels ? cat_of_label : nullptr; g.shape_cat = labels ? shape_cat : nullptr; g.N = rows_per_shape;
+    rows_dispatch<ROWS_MAX_K0 / 8>(K0 / 8, g, as_stream(stream));
     return prifit_check_launch();
 }
 

@@ -3,6 +3,7 @@
     frozen = prifit_amd.inference.freeze(model)      # models.pointnet2_part_seg_msg.get_model, reconstruct=False
     seg, (l1, l2, l3), feat, zero, zero = frozen(xyz, cls_label, fps_start=None)
     seg = frozen.predict(xyz, cls_label)             # [B, N, num_parts] log-probabilities
+    part = frozen.labels(xyz, cls_label, shape_cat, cat_of_label)   # [B, N] int32 part labels, one launch for the tail
     frozen.refresh()                                 # re-fold from the live model (after more training)
 
 With fixed statistics a BatchNorm is a per-channel affine: s = gamma / sqrt(var + eps), bn(W x + b) = (s W) x + ((b - mean) s + beta).
@@ -14,7 +15,8 @@ The forward then runs on that buffer alone, under no_grad:
   * layers 2 and 3 of every SA1 / SA2 scale and the max over the samples: one launch each (prifit_mlp_chain_pool_f32), no
     [P, C] tensor written, the pooled rows side by side in the level's output;
   * SA3, the feature-propagation stacks and the head: one folded product per layer on prifit_gemm_f32 (bias, ReLU on load
-    through a unit-scale a_affine), then the existing pool / affine launch.
+    through a unit-scale a_affine), then the existing pool / affine launch;
+  * labels() only: fp1, conv1 + bn1, conv2 and the category-restricted arg-max in one launch (prifit_mlp_chain_rows_f32).
 No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
 to the live model: a shape the kernels do not take is an error."""
 import ctypes
@@ -25,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import nn_ops, ops, profiler
-from ._lib import call, cur_stream, ptr, query
+from ._lib import call, cur_stream, dll, ptr, query
 from .models import pointnet2_part_seg_msg as _msg
 from .models.pointnet_util import _col_index, _pad4
 
@@ -119,6 +121,14 @@ class FrozenPartSeg(nn.Module):
             d2 = st[-1].cout
         self._head = stack([model.conv1], [model.bn1])
         self._conv2, self._emb = stack([model.conv2, model.extra_conv_emb], [None, None])
+        # labels(): fp1's rows padded to a multiple of 8 columns (the chain's k step); its first-layer weight in that order
+        # is fp1's own packed copy where 4 and 8 pad alike (150 -> 152), one more packed copy otherwise (153 -> 160)
+        st, w0, d1, d2 = self._fp["fp1"]
+        kp, kp8 = _pad4(d1 + d2), (d1 + d2 + 7) // 8 * 8
+        cols8 = list(range(d1, d1 + d2)) + list(range(d1)) + [-1] * (kp8 - d1 - d2)
+        self._tail_w0 = w0 if kp8 == kp else _first_weight(st[0], cols8, packs)
+        self._tail_kp = kp8
+        self._tail = list(st) + list(self._head) + [self._conv2]
         self._layers, self._packs = layers, packs
         if len(layers) > query("prifit_fold_bn_max_jobs"):
             raise TypeError("freeze(): %d layers, prifit_fold_bn takes %d" % (len(layers), query("prifit_fold_bn_max_jobs")))
@@ -224,7 +234,9 @@ class FrozenPartSeg(nn.Module):
     def predict(self, xyz, cls_label, fps_start=None):
         return self.forward(xyz, cls_label, fps_start)[0]
 
-    def _forward(self, xyz, cls_label, fps_start, embed):
+    def _trunk(self, xyz, cls_label, fps_start):
+        """Everything in front of fp1, shared by forward() and labels(): the three set-abstraction levels, fp3 and fp2.
+        -> (pts [B,N,C], l0_xyz, l1_xyz, skip [B,N,16+3+C], l1_up, l2_up, l3_points)."""
         self._bind()
         B, _, N = xyz.shape
         pts = xyz.permute(0, 2, 1).contiguous().float()
@@ -244,6 +256,11 @@ class FrozenPartSeg(nn.Module):
         l1_up = self._fp_level("fp2", l1_xyz, l2_xyz, l1_points, l2_up)
         onehot = cls_label.reshape(B, 1, 16).expand(B, N, 16).to(pts.dtype)
         skip = torch.cat([onehot, l0_xyz, pts], dim=-1)
+        return pts, l0_xyz, l1_xyz, skip, l1_up, l2_up, l3_points
+
+    def _forward(self, xyz, cls_label, fps_start, embed):
+        B, _, N = xyz.shape
+        pts, l0_xyz, l1_xyz, skip, l1_up, l2_up, l3_points = self._trunk(xyz, cls_label, fps_start)
         l0_up = self._fp_level("fp1", l0_xyz, l1_xyz, skip, l1_up)
         feat = torch.empty(B * N, self._head[0].cout, dtype=torch.float32, device=pts.device)
         self._stack(l0_up.reshape(B * N, -1), False, self._head, self._head[0].W, 0, feat)
@@ -254,6 +271,59 @@ class FrozenPartSeg(nn.Module):
         if embed:
             outs += (None, None, self._linear(feat, self._emb).reshape(B, N, -1).permute(0, 2, 1))
         return outs
+
+    def _tail_shape(self):
+        """(K0, widths) of the per-point tail; NotImplementedError where prifit_mlp_chain_rows_f32 does not take it."""
+        K0, widths = self._tail_kp, [ly.cout for ly in self._tail]
+        L = len(widths)
+        if not dll().prifit_mlp_chain_rows_supported(K0, L, (ctypes.c_int32 * L)(*widths)):
+            raise NotImplementedError("FrozenPartSeg.labels(): a tail of %d input columns and widths %s is outside "
+                                      "prifit_mlp_chain_rows_f32 (4 layers, 128 / 128 / 128 / at most 64 parts, at most 160 "
+                                      "columns); there is no fall-back" % (K0, tuple(widths)))
+        return K0, widths
+
+    def labels(self, xyz, cls_label, shape_cat=None, cat_of_label=None, fps_start=None, return_scores=False):
+        """Part labels straight from the frozen network: xyz [B, C, N], cls_label as forward() -> labels [B, N] int32, with
+        return_scores=True also scores [B, N, num_parts], conv2's outputs BEFORE log_softmax (which moves no maximum).
+        shape_cat int [B] (device or host) and cat_of_label int [num_parts] restrict each cloud's arg-max to the parts of
+        its category, testing.py:141-144 -- an evaluation loop passes SegmentationEvaluator.cat_of_label and
+        cat_of_label[target[:, 0]]; a cloud whose category has no part gets -1.  Both None: the arg-max over all parts.
+        The first maximum wins, a NaN beats every number (prifit_seg_metrics' rules, bit for bit).
+        forward()'s route up to fp1's rows, then ONE launch (prifit_mlp_chain_rows_f32) over fp1's two layers, conv1 + bn1
+        and conv2: no [B N, 128] tensor, no log_softmax.  No fall-back: NotImplementedError for a tail the kernel refuses."""
+        if (shape_cat is None) != (cat_of_label is None):
+            raise ValueError("FrozenPartSeg.labels(): shape_cat and cat_of_label go together (both or neither)")
+        if xyz.dim() != 3:
+            raise ValueError("FrozenPartSeg.labels(): xyz must be [B, C, N], got %s" % (tuple(xyz.shape),))
+        B, _, N = xyz.shape
+        K0, widths = self._tail_shape()
+        parts = widths[-1]
+        if shape_cat is not None:
+            shape_cat, cat_of_label = torch.as_tensor(shape_cat), torch.as_tensor(cat_of_label)
+            for name, t, n in (("shape_cat", shape_cat, B), ("cat_of_label", cat_of_label, parts)):
+                if t.dtype.is_floating_point or t.dtype == torch.bool or t.numel() != n:
+                    raise ValueError("FrozenPartSeg.labels(): %s must hold %d integers, got %s %s"
+                                     % (name, n, t.dtype, tuple(t.shape)))
+        with torch.no_grad():
+            pts, l0_xyz, l1_xyz, skip, l1_up, _, _ = self._trunk(xyz, cls_label, fps_start)
+            dev = pts.device
+            if shape_cat is not None:
+                shape_cat = shape_cat.reshape(B).to(device=dev, dtype=torch.int32).contiguous()
+                cat_of_label = cat_of_label.reshape(parts).to(device=dev, dtype=torch.int32).contiguous()
+            rows = self._fp_rows("fp1", l0_xyz, l1_xyz, skip, l1_up, K0)
+            P, L = B * N, len(widths)
+            out = torch.empty(B, N, dtype=torch.int32, device=dev)
+            scores = torch.empty(B, N, parts, dtype=torch.float32, device=dev) if return_scores else None
+            Ws = [self._tail_w0.W] + [ly.W for ly in self._tail[1:]]
+            nws = dll().prifit_mlp_chain_rows_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
+            ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
+            flops = 2.0 * P * sum(k * c for k, c in zip([K0] + widths[:-1], widths))
+            with profiler.span(profiler.tag("mlp_chain_rows", P, K0, *widths), flops):
+                call("prifit_mlp_chain_rows_f32", ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths),
+                     nn_ops._ptr_array(Ws), (ctypes.c_longlong * L)(*[W.stride(0) for W in Ws]),
+                     nn_ops._ptr_array([ly.b for ly in self._tail]), ptr(scores), _LL(parts), ptr(out), ptr(cat_of_label),
+                     ptr(shape_cat), N, ptr(ws), cur_stream())
+        return (out, scores) if return_scores else out
 
     def _rows(self, parts, B, n, kp):
         """[B n, kp] rows = the parts side by side, zero padded (the zeros are the flat buffer's: no fill launch)."""
@@ -352,19 +422,25 @@ class FrozenPartSeg(nn.Module):
 
     def _fp_level(self, name, xyz1, xyz2, points1, points2):
         """Feature propagation: xyz1 [B,N,3], xyz2 [B,S,3] (None: S == 1), points1 [B,N,D1], points2 [B,S,D2] -> [B,N,C]."""
-        st, w0, D1, D2 = self._fp[name]
+        st, w0, _, _ = self._fp[name]
+        B, N, _ = xyz1.shape
+        rows = self._fp_rows(name, xyz1, xyz2, points1, points2, w0.W.shape[1])
+        out = torch.empty(B * N, st[-1].cout, dtype=torch.float32, device=xyz1.device)
+        self._stack(rows, False, st, w0.W, 0, out)
+        return out.reshape(B, N, -1)
+
+    def _fp_rows(self, name, xyz1, xyz2, points1, points2, kp):
+        """The input rows of a feature-propagation stack, [B N, kp] = [interpolated (D2) | points1 (D1) | 0]: 3-NN and one launch."""
+        _, _, D1, D2 = self._fp[name]
         B, N, _ = xyz1.shape
         S = points2.shape[1]
-        kp = w0.W.shape[1]
         idx = w = None
         if S > 1:
             idx, w = ops.three_nn(xyz1, xyz2)
         points1, points2 = points1.contiguous(), points2.contiguous()
         rows = torch.empty(B * N, kp, dtype=torch.float32, device=xyz1.device)
         call("prifit_fp_rows", ptr(points2), ptr(idx), ptr(w), ptr(points1), B, N, S, D2, D1, kp, ptr(rows), cur_stream())
-        out = torch.empty(B * N, st[-1].cout, dtype=torch.float32, device=xyz1.device)
-        self._stack(rows, False, st, w0.W, 0, out)
-        return out.reshape(B, N, -1)
+        return rows
 
 
 def freeze(model):

@@ -4,13 +4,18 @@ model of prifit_amd.inference on the same weights, inputs and sampling starts; t
 (prifit_mlp_chain_pool_f32) against the launches it replaces (SharedMLPFn in eval mode on the same first-layer rows: the
 coefficient arithmetic, two products, the pool).  Every arm sees the same seeded state in every repeat; the arms alternate
 within a round (the box is shared) and the table gives the median and the (min .. max) of the rounds.  The outputs of the two
-arms are compared before anything is timed.
-usage (GPU box): python tools/bench_infer.py [repetitions, default 20] [rounds, default 5] [output file, default profiles/infer.txt]"""
-import os, sys
+arms are compared before anything is timed.  Then the part labels: (c) frozen.predict() followed by the torch restricted
+arg-max of SegmentationEvaluator.predict -- the only way to labels before FrozenPartSeg.labels() -- against (d) frozen.labels(),
+and the row chain (prifit_mlp_chain_rows_f32) alone against the launches it replaces on the same fp1 rows; written to a
+second file.
+usage (GPU box): python tools/bench_infer.py [repetitions, default 20] [rounds, default 5] [output file, default profiles/infer.txt]
+                                             [labels output file, default profiles/infer_labels.txt]"""
+import ctypes, os, sys
 import numpy as np, torch
+import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from prifit_amd import inference
+from prifit_amd import inference, nn_ops, testing as T
 from prifit_amd._lib import call, cur_stream, ptr, query
 from prifit_amd.models import pointnet2_part_seg_msg as M
 from prifit_amd.nn_ops import FrontEnd, SharedMLPFn
@@ -19,6 +24,7 @@ B, N = 24, 2048
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 out_path = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "infer.txt")
+labels_path = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", "infer_labels.txt")
 dev = torch.device("cuda", 0)
 
 
@@ -117,3 +123,70 @@ print("\n".join(lines))
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
     f.write("\n".join(lines) + "\n")
+
+# ---- part labels: (c) the parent's way -- frozen.predict() and the torch restricted arg-max of SegmentationEvaluator.predict
+# -- against (d) frozen.labels(); then the row chain alone against the launches it replaces, on the same fp1 rows
+ev = T.SegmentationEvaluator()
+col_host = ev.cat_of_label
+shape_cat = onehot.reshape(B, 16).argmax(dim=1)
+first = torch.stack([(col_host == int(c)).nonzero()[0, 0] for c in shape_cat.cpu()])
+target = first.view(B, 1).expand(B, N).contiguous().to(dev)              # target[:, 0] selects the category, as in testing.py:142
+col_dev = col_host.to(torch.int32).to(dev)
+cat_dev = shape_cat.to(torch.int32)
+
+
+def old_labels():
+    return ev.predict(frozen.predict(xyz, onehot, fps_start=start), target)[0]
+
+
+def new_labels():
+    return frozen.labels(xyz, onehot, cat_dev, col_dev, fps_start=start)
+
+
+c, d = old_labels(), new_labels()
+torch.cuda.synchronize()
+agree = float((c == d.long()).float().mean())
+(c_ms, c_lo, c_hi), (d_ms, d_lo, d_hi) = alternate([old_labels, new_labels], 3, reps, rounds)
+lab = ["part labels, B = %d x N = %d, %d repetitions x %d alternating rounds (median, min .. max), %s"
+       % (B, N, reps, rounds, torch.cuda.get_device_name(0)),
+       "labels of the two arms equal on %.4f %% of the points" % (100.0 * agree),
+       "(c) frozen.predict() + torch restricted arg-max   %8.3f ms  (%.3f .. %.3f)" % (c_ms, c_lo, c_hi),
+       "(d) frozen.labels()                               %8.3f ms  (%.3f .. %.3f)" % (d_ms, d_lo, d_hi),
+       "ratio (c) / (d)                                   %8.2fx%s"
+       % (c_ms / d_ms, "" if d_ms <= c_hi else "  (labels() NOT faster)")]
+
+tail, K0 = frozen._tail, frozen._tail_kp
+widths = [ly.cout for ly in tail]
+P = B * N
+rows = torch.randn(P, K0, device=dev)
+rows4 = rows[:, :frozen._fp["fp1"][1].W.shape[1]].contiguous()            # the rows forward() builds: padded to 4, not 8
+Ws = [frozen._tail_w0.W] + [ly.W for ly in tail[1:]]
+out = torch.empty(P, dtype=torch.int32, device=dev)
+allowed = col_dev.view(1, 1, -1) == cat_dev.view(-1, 1, 1)
+
+
+def replaced_tail():
+    st, w0, _, _ = frozen._fp["fp1"]
+    l0_up = torch.empty(P, st[-1].cout, device=dev)
+    frozen._stack(rows4, False, st, w0.W, 0, l0_up)
+    feat = torch.empty(P, frozen._head[0].cout, device=dev)
+    frozen._stack(l0_up, False, frozen._head, frozen._head[0].W, 0, feat)
+    seg = F.log_softmax(frozen._linear(feat, frozen._conv2), dim=1).reshape(B, N, -1)
+    return seg.masked_fill(~allowed, float("-inf")).argmax(dim=-1)
+
+
+def chain_rows():
+    call("prifit_mlp_chain_rows_f32", ptr(rows), K0, P, K0, 4, (ctypes.c_int32 * 4)(*widths), nn_ops._ptr_array(Ws),
+         (ctypes.c_longlong * 4)(*[W.stride(0) for W in Ws]), nn_ops._ptr_array([ly.b for ly in tail]), None, widths[-1], ptr(out),
+         ptr(col_dev), ptr(cat_dev), N, None, cur_stream())
+
+
+(r_ms, r_lo, r_hi), (k_ms, k_lo, k_hi) = alternate([replaced_tail, chain_rows], 3, reps, rounds)
+flops = 2.0 * P * sum(k * c for k, c in zip([K0] + widths[:-1], widths))
+lab += ["", "the tail alone on %d fp1 rows (K0 = %d, widths %s): 4 products, 2 ReLU launches, log_softmax, masked arg-max" % (P, K0, tuple(widths)),
+        "replaced launches        %8.3f ms  (%.3f .. %.3f)" % (r_ms, r_lo, r_hi),
+        "prifit_mlp_chain_rows_f32 %7.3f ms  (%.3f .. %.3f)   %5.2fx   %4.1f %% of the fp32 MFMA peak (157.3 TF)%s"
+        % (k_ms, k_lo, k_hi, r_ms / k_ms, 100.0 * flops / (k_ms * 1e-3) / 157.3e12, "" if k_ms <= r_hi else "  (chain NOT faster)")]
+print("\n".join(lab))
+with open(labels_path, "w") as f:
+    f.write("\n".join(lab) + "\n")
