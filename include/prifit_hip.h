@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 801
+#define PRIFIT_ABI_VERSION 802
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1076,6 +1076,51 @@ int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0
                               const float *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
                               int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
                               float *workspace, void *stream);
+
+/* ---- frozen inference with bf16 arithmetic (FrozenPartSeg(model, precision="bf16")) ---- */
+
+/* Folded fp32 weights -> bf16 for the chains below, ONE launch for up to prifit_pack_bf16_max_jobs() layers (HOST arrays of
+ * njobs entries each, read before the call returns; the jobs travel by value like those of prifit_fold_bn).  Job j: w [rows,
+ * ldw] fp32 with `cols` <= ldw input columns (a folded W' of prifit_fold_bn or a packed copy of prifit_pack_cols_multi) ->
+ * out [rows, ldk] of 16-bit patterns, ldk = cols rounded up to a multiple of 16, contiguous, 16-byte aligned.
+ * The rounding is to nearest even, a value beyond the bf16 range becomes +-inf: tensor.to(torch.bfloat16), bit for bit; a
+ * NaN becomes the NaN 0x7fc0 (c10::BFloat16's scalar conversion).  Columns cols .. ldk - 1 are 0.  order[j] picks the column order, 16 columns (one k-step of
+ * v_mfma_f32_32x32x16_bf16) at a time, so that a lane's 8 elements of a k-step are 16 consecutive bytes:
+ *   0  plain: out[c][p] = w[c][p] -- a first layer, whose other operand is loaded from memory in that order;
+ *   1  accumulator order: out[c][16t + 8h + e] = w[c][16t + 8(e >> 2) + 4h + (e & 3)] (h = 0, 1; e = 0 .. 7) -- a layer fed by the
+ *      previous product's C/D registers, whose element e of lane half h in k-step t is that channel.
+ * PRIFIT_EINVAL without a launch: njobs < 1 or > prifit_pack_bf16_max_jobs(), a NULL array or entry, rows or cols < 1,
+ * ldw < cols, order not 0 or 1, out[j] not 16-byte aligned.  The regions of different jobs must not overlap. */
+int prifit_pack_bf16_max_jobs(void);
+int prifit_pack_bf16_multi(int njobs, const float *const *w, const int32_t *rows, const int32_t *cols, const int32_t *ldw,
+                           const int32_t *order, uint16_t *const *out, void *stream);
+
+/* prifit_mlp_chain_pool_f32 with bf16 products: the same contract, the same five (C0, C1, C2) with pool_K in {32, 64, 128},
+ * X fp32 [G * pool_K, ldx] (ReLU on load), b1 / b2 fp32, out fp32 -- but W1 [C1, ldw1] and W2 [C2, ldw2] are bf16 as
+ * prifit_pack_bf16_multi writes them, W1 in the plain order and W2 in the accumulator order (ldw1 >= C0 and ldw2 >= C1, each
+ * rounded up to 16; multiples of 8 elements; 16-byte aligned).  Every layer INPUT is rounded to bf16 (nearest even) before
+ * its product -- relu(X) and relu(W1 . + b1) -- the products accumulate in fp32 (v_mfma_f32_32x32x16_bf16), the max over a
+ * group's rows is taken on the fp32 accumulators of the last layer, bias and ReLU after it.  No [P, C] tensor is written.
+ * _supported answers as prifit_mlp_chain_pool_supported; _workspace: floats of `workspace` the call needs (0 today). */
+int prifit_mlp_chain_pool_bf16_supported(int C0, int C1, int C2, int pool_K);
+long long prifit_mlp_chain_pool_bf16_workspace(int G, int pool_K, int C0, int C1, int C2);
+int prifit_mlp_chain_pool_bf16(const float *X, long long ldx, int G, int pool_K, int C0, int C1, int C2, const uint16_t *W1,
+                               long long ldw1, const float *b1, const uint16_t *W2, long long ldw2, const float *b2, float *out,
+                               long long ldo, float *workspace, void *stream);
+
+/* prifit_mlp_chain_rows_f32 with bf16 products: the same contract (L == 4, widths (128, 128, 128, C_L), 1 <= C_L <= 64,
+ * K0 % 8 == 0, 8 <= K0 <= 160; raw fp32 rows, a NaN kept by every ReLU; scores fp32 = the last layer's fp32 accumulators
+ * plus its fp32 bias; labels by the same code as the fp32 entry point, bit for bit on equal scores) -- but W_l are bf16 as
+ * prifit_pack_bf16_multi writes them, W_1 [128, ldw_1 >= K0 rounded up to 16] in the plain order and W_2 .. W_4 (ldw_l >= 128)
+ * in the accumulator order; every ldw_l a multiple of 8 elements, every W_l 16-byte aligned.  Every layer input is rounded
+ * to bf16 before its product; where K0 % 16 == 8 the last k-step's upper half is not loaded (nothing behind a row's K0
+ * columns is read).  A row >= P is computed on a copy of row P - 1 and stores nothing.  PRIFIT_EINVAL as the fp32 entry point. */
+int prifit_mlp_chain_rows_bf16_supported(int K0, int L, const int32_t *widths);
+long long prifit_mlp_chain_rows_bf16_workspace(long long P, int K0, int L, const int32_t *widths);
+int prifit_mlp_chain_rows_bf16(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                               const uint16_t *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
+                               int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
+                               float *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,7 @@ SOURCES = {
     "augment.hip": ["-ffp-contract=off"],
     "seg_metrics.hip": [],
     "infer.hip": [],
+    "infer_bf16.hip": [],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],
     "comm.hip": [],        # host-only: the RCCL export (RCCL itself is resolved with dlopen at run time)

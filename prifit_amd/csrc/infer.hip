@@ -15,11 +15,10 @@
 // the pre-activation it loads to the pooled maximum without LDS, without a barrier and without a shuffle; the only
 // cross-lane traffic is the max over the 32 rows at the very end (DPP) and 4 C2 floats of LDS per workgroup to combine the
 // waves of a pooling group.  The weights are read from L2 / L1 as MFMA fragments (W1' + W2' are 12 .. 300 KB per scale).
+// What follows the last product of a chain is shared with the bf16 kernels of infer_bf16.hip: infer_chain.h.
 #include <algorithm>
 
-#include "common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "infer_chain.h"
 
 namespace {
 
@@ -76,28 +75,6 @@ struct ChainArgs {
     float *out;
     long long ldo;
 };
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ float dpp_max(float v)
-{
-    const int o = __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), CTRL, ROWMASK, 0xf, false);
-    return fmaxf(v, __builtin_bit_cast(float, o));
-}
-
-// max over the 32 lanes of each half of the wave (lanes 0..31 and 32..63 separately); valid in lanes 16..31 and 48..63
-__device__ __forceinline__ float half_wave_max(float v)
-{
-    v = dpp_max<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-    v = dpp_max<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-    v = dpp_max<0x124, 0xf>(v);   // row_ror:4
-    v = dpp_max<0x128, 0xf>(v);   // row_ror:8  -> every lane holds the max of its row of 16
-    v = dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3 -> they hold the max of rows 0 + 1 / 2 + 3
-    return v;
-}
-
-constexpr int CHAIN_ROWS = 128;   // rows per workgroup: 4 waves x 32
 
 // X [P, C0] (pre-activation of layer 1, ReLU on load) -> out[g, :] = max over the pool_K rows of group g of
 // relu(W2 relu(W1 relu(x) + b1) + b2); W1 [C1, ldw1], W2 [C2, ldw2].  C0 % 8 == 0, C1 % 4 == 0, C2 % 32 == 0,
@@ -175,32 +152,11 @@ __global__ __launch_bounds__(256) void mlp_chain_pool_kernel(const ChainArgs g)
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h[b][4 * gq + 3], acc, 0, 0, 0);
                 }
             }
-            // max over rows first, bias and ReLU on the maximum: x -> relu(x + b) is non-decreasing in fp32, so the two commute exactly
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = half_wave_max(acc[r]);
-            if (li == 31) {
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int c0 = 32 * b2 + 8 * gq + 4 * lh;
-                    const float4 bb = ld4(g.b2 + c0);
-                    *reinterpret_cast<float4 *>(&s_pool[wave][c0]) =
-                        make_float4(fmaxf(acc[4 * gq + 0] + bb.x, 0.f), fmaxf(acc[4 * gq + 1] + bb.y, 0.f),
-                                    fmaxf(acc[4 * gq + 2] + bb.z, 0.f), fmaxf(acc[4 * gq + 3] + bb.w, 0.f));
-                }
-            }
+            chain_pool_block(acc, g.b2, b2, li, lh, s_pool[wave]);
         }
     }
     __syncthreads();
-    // the waves of a pooling group: pool_K / 32 neighbours (a live group has all of them: P = G * pool_K)
-    const int wpg = g.pool_K >> 5, gpt = CHAIN_ROWS / g.pool_K;
-    for (int id = threadIdx.x; id < gpt * C2; id += 256) {
-        const int gi = id / C2, c = id - gi * C2;
-        const long long grp = (long long)blockIdx.x * gpt + gi;
-        if (grp >= g.G) break;
-        float v = s_pool[gi * wpg][c];
-        for (int w = 1; w < wpg; ++w) v = fmaxf(v, s_pool[gi * wpg + w][c]);
-        g.out[grp * g.ldo + c] = v;
-    }
+    chain_pool_groups<C2>(s_pool, g.G, g.pool_K, g.out, g.ldo);
 }
 
 template <int C0, int C1, int C2>
@@ -210,49 +166,13 @@ void chain_launch(const ChainArgs &g, hipStream_t st)
     hipLaunchKernelGGL((mlp_chain_pool_kernel<C0, C1, C2>), dim3(grid), dim3(256), 0, st, g);
 }
 
-int chain_shape(int C0, int C1, int C2)
-{
-    static const int shapes[5][3] = {{32, 32, 64}, {64, 64, 128}, {64, 96, 128}, {128, 128, 256}, {128, 196, 256}};
-    for (int i = 0; i < 5; ++i)
-        if (shapes[i][0] == C0 && shapes[i][1] == C1 && shapes[i][2] == C2) return i;
-    return -1;
-}
-
-bool mis16(const void *p) { return ((uintptr_t)p & 15) != 0; }
-
 // ---- the per-point tail of the part-segmentation network: four layers over raw rows, scores and / or part labels out
 //
 // The layout argument above does not stop at two layers: whatever the depth, the C/D registers of one transposed product
 // are the B operand of the next, as long as the next weight is read at columns 32b + 8g + 4h + m.  So a wave carries its 32
 // rows through fp1's two layers, conv1 + bn1 and conv2 in registers; the last product's C/D layout leaves lane (j, h) with
 // the scores of channels 32b + 8g + 4h + m of row j, which it ranks itself before one exchange with lane j of the other half.
-constexpr int ROWS_L = 4, ROWS_W = 128, ROWS_NB = ROWS_W / 32, ROWS_MAX_CL = 64, ROWS_MAX_K0 = 160;
-
-struct RowsArgs {
-    const float *X;
-    long long ldx, P;
-    const float *W[ROWS_L], *b[ROWS_L];
-    long long ldw[ROWS_L];
-    int CL;
-    float *scores;
-    long long lds;
-    int32_t *labels;
-    const int32_t *cat_of_label, *shape_cat;     // shape_cat NULL: every channel < CL is allowed
-    int N;                                       // rows per shape
-};
-
-// ReLU that keeps a NaN (np.maximum, torch.relu): a NaN input row reaches the scores, where the arg-max rule ranks it
-__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
-
-// order-preserving key of a score among the ALLOWED channels: score_key of seg_metrics.hip, bit for bit (NaN = the largest
-// key, -0 = +0, always >= 0x007fffff so that 0 is free for the channels outside the window)
-__device__ __forceinline__ unsigned rows_score_key(float x)
-{
-    const unsigned u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    if ((u << 1) == 0) return 0x80000000u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+typedef RowsArgsT<float> RowsArgs;
 
 // one 128 -> 128 layer on the registers: out = relu(W in + bias), both in the C/D layout (block b, register 4g + m of lane
 // (j, h) = channel 32b + 8g + 4h + m of row j)
@@ -295,10 +215,7 @@ __global__ __launch_bounds__(256) void mlp_chain_rows_kernel(const RowsArgs g)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int li = lane & 31, lh = lane >> 5;
     const int CL = g.CL;
-    if (g.labels && g.shape_cat) {                // (grid-uniform) the category table, once per workgroup
-        if (threadIdx.x < ROWS_MAX_CL) s_cat[threadIdx.x] = threadIdx.x < CL ? g.cat_of_label[threadIdx.x] : 0;
-        __syncthreads();                          // the only barrier, before the chain starts
-    }
+    rows_load_cats(g, s_cat);
     const long long row0 = (long long)blockIdx.x * CHAIN_ROWS + 32 * wave;
     if (row0 >= g.P) return;                      // wave-uniform
     const long long row = row0 + li;
@@ -339,9 +256,7 @@ __global__ __launch_bounds__(256) void mlp_chain_rows_kernel(const RowsArgs g)
     rows_layer(g.W[2], g.ldw[2], g.b[2], hb, ha, li, lh);
 
     // layer 4, no ReLU: channels >= CL are zero A rows (the row index clamped for the load, the value zeroed)
-    const bool vec = g.scores && !(g.lds & 3) && !((uintptr_t)g.scores & 15);      // grid-uniform: float4 stores are aligned
-    const int cat = (g.labels && g.shape_cat) ? g.shape_cat[(int)rowc / g.N] : 0;      // P <= 2^31 - 1
-    unsigned long long best = 0;                  // (key << 32) | (63 - channel): the larger key, then the lower channel
+    RowsRank rk = rows_rank_begin(g, rowc);
 #pragma unroll
     for (int b2 = 0; b2 < ROWS_MAX_CL / 32; ++b2) {
         if (32 * b2 >= CL) break;                 // grid-uniform
@@ -361,41 +276,9 @@ __global__ __launch_bounds__(256) void mlp_chain_rows_kernel(const RowsArgs g)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, ha[b][4 * gq + 3], acc, 0, 0, 0);
             }
         }
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int c0 = 32 * b2 + 8 * gq + 4 * lh;
-            float z[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) z[m] = acc[4 * gq + m] + (c0 + m < CL ? g.b[3][c0 + m] : 0.f);
-            if (g.scores && live) {
-                float *sr = g.scores + row * g.lds + c0;
-                if (vec && c0 + 4 <= CL) *reinterpret_cast<float4 *>(sr) = make_float4(z[0], z[1], z[2], z[3]);
-                else {
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-                        if (c0 + m < CL) sr[m] = z[m];
-                }
-            }
-            if (g.labels) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {     // ascending channels within the lane: > keeps the first maximum
-                    const int ch = c0 + m;
-                    // a negative category is none (prifit_seg_metrics' shape_cat -1), whatever cat_of_label holds
-                    const bool allowed = ch < CL && (!g.shape_cat || (cat >= 0 && s_cat[ch < ROWS_MAX_CL ? ch : 0] == cat));
-                    const unsigned long long k =
-                        allowed ? ((unsigned long long)rows_score_key(z[m]) << 32) | (unsigned)(63 - ch) : 0ull;
-                    best = k > best ? k : best;
-                }
-            }
-        }
+        rows_emit(g, acc, b2, lh, row, live, s_cat, rk);
     }
-    if (g.labels) {
-        // lanes j and j + 32 hold the two halves of row j's channels: one exchange, the tie goes to the lower channel
-        const unsigned hi = __shfl_xor((unsigned)(best >> 32), 32), lo = __shfl_xor((unsigned)best, 32);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        best = other > best ? other : best;
-        if (lh == 0 && live) g.labels[row] = (best >> 32) ? 63 - (int)(best & 63u) : -1;
-    }
+    rows_finish(g, rk, lh, row, live);
 }
 
 template <int KQ>
@@ -498,13 +381,9 @@ int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0
                               float *workspace, void *stream)
 {
     (void)workspace;
-    if (!prifit_mlp_chain_rows_supported(K0, L, widths) || !X || !W || !ldw || !b || (!scores && !labels) || P < 1 ||
-        P > 0x7fffffffLL || ldx < K0 || (ldx & 3) || mis16(X) || rows_per_shape <= 0)
+    if (rows_check(K0, L, widths, X, ldx, P, W, ldw, b, scores, lds, labels, cat_of_label, shape_cat, rows_per_shape))
         return PRIFIT_EINVAL;
     const int CL = widths[ROWS_L - 1];
-    if (scores && lds < CL) return PRIFIT_EINVAL;
-    if (labels && (shape_cat != nullptr) != (cat_of_label != nullptr)) return PRIFIT_EINVAL;
-    if (labels && shape_cat && P % rows_per_shape) return PRIFIT_EINVAL;
     RowsArgs g = {};
     for (int l = 0; l < ROWS_L; ++l) {
         const int kin = l ? ROWS_W : K0;

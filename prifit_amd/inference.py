@@ -1,6 +1,7 @@
 """Frozen inference for the MSG part-segmentation network.
 
     frozen = prifit_amd.inference.freeze(model)      # models.pointnet2_part_seg_msg.get_model, reconstruct=False
+    frozen = prifit_amd.inference.freeze(model, precision="bf16")     # the on-chip chains on the 16-bit matrix pipe (3.9.2)
     seg, (l1, l2, l3), feat, zero, zero = frozen(xyz, cls_label, fps_start=None)
     seg = frozen.predict(xyz, cls_label)             # [B, N, num_parts] log-probabilities
     part = frozen.labels(xyz, cls_label, shape_cat, cat_of_label)   # [B, N] int32 part labels, one launch for the tail
@@ -18,7 +19,13 @@ The forward then runs on that buffer alone, under no_grad:
     through a unit-scale a_affine), then the existing pool / affine launch;
   * labels() only: fp1, conv1 + bn1, conv2 and the category-restricted arg-max in one launch (prifit_mlp_chain_rows_f32).
 No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
-to the live model: a shape the kernels do not take is an error."""
+to the live model: a shape the kernels do not take is an error.
+
+precision="bf16"  changes the arithmetic of the two on-chip chains only: prifit_mlp_chain_pool_bf16 and
+prifit_mlp_chain_rows_bf16 round every layer input to bf16 and accumulate in fp32 (v_mfma_f32_32x32x16_bf16).  Their weights
+are a second flat buffer of 16-bit patterns, written by ONE more launch of refresh() (prifit_pack_bf16_multi) in the column
+order the MFMA reads; the biases stay fp32 in `flat`.  Everything else -- sampling, grouping + first conv, the by-linearity
+products, SA3, fp3 / fp2, 3-NN, the separate-launch tail of forward() -- is the fp32 module's, launch for launch."""
 import ctypes
 
 import numpy as np
@@ -33,6 +40,8 @@ from .models.pointnet_util import _col_index, _pad4
 
 _LL = ctypes.c_longlong
 _ALIGN = 64      # floats: every region of the flat buffer starts on a 256-byte boundary
+_ALIGN16 = 128   # 16-bit words: likewise in the bf16 buffer
+PRECISIONS = ("fp32", "bf16")
 
 
 class _Folded:
@@ -56,6 +65,18 @@ class _Packed:
         self.W = None
 
 
+class _Bf16:
+    """The bf16 copy of a chained layer's weight: `src` (a _Folded or a _Packed) with `cols` input columns -> [cout, ldk]
+    16-bit patterns at `off` of the bf16 buffer, ldk = cols rounded up to 16; order 0: plain columns (a first layer, fed
+    from memory), 1: the accumulator order (a layer fed by the previous product's registers)."""
+
+    def __init__(self, src, cout, cols, order):
+        self.src, self.cout, self.cols, self.order = src, cout, cols, order
+        self.ldk = (cols + 15) // 16 * 16
+        self.off = -1
+        self.W = None
+
+
 def _first_weight(layer, cols, packs):
     """The folded weight of `layer` in the column order `cols`: the fold's own rows when that is what they are (the fold
     pads a row with zero columns to a multiple of 4), else a packed copy."""
@@ -70,8 +91,11 @@ def _first_weight(layer, cols, packs):
 class FrozenPartSeg(nn.Module):
     """The eval-mode forward of a `pointnet2_part_seg_msg.get_model` on folded weights; see the module docstring."""
 
-    def __init__(self, model):
+    def __init__(self, model, precision="fp32"):
         super().__init__()
+        if precision not in PRECISIONS:
+            raise ValueError("FrozenPartSeg: precision must be one of %s, got %r" % (", ".join(PRECISIONS), precision))
+        self.precision = precision
         if not isinstance(model, _msg.get_model):
             raise TypeError("freeze() takes a models.pointnet2_part_seg_msg.get_model (the SSG, cls, sem-seg and DGCNN networks "
                             "have no frozen form), got %s" % type(model).__name__)
@@ -155,6 +179,24 @@ class FrozenPartSeg(nn.Module):
         flat[self._ones_off:self._ones_off + self._unit_c] = 1.0
         flat[self._zeros_off:self._zeros_off + self._unit_c] = 0.0
         self.flat = nn.Parameter(flat, requires_grad=False)
+        # bf16 only: the chained layers' weights as 16-bit patterns -- an integer buffer, so that .float() / .half() on
+        # the module cannot reinterpret it
+        self._bf16 = []
+        if precision == "bf16":
+            chained = lambda st: [_Bf16(st[1], st[1].cout, st[1].kin, 0), _Bf16(st[2], st[2].cout, st[2].kin, 1)]
+            for lv in self._sa:
+                lv["bf16"] = [chained(st) for st, _ in lv["scales"]]
+                self._bf16 += [w for pair in lv["bf16"] for w in pair]
+            self._tail_bf16 = [_Bf16(self._tail_w0, self._tail[0].cout, self._tail_kp, 0)] + \
+                              [_Bf16(ly, ly.cout, ly.kin, 1) for ly in self._tail[1:]]
+            self._bf16 += self._tail_bf16
+            if len(self._bf16) > query("prifit_pack_bf16_max_jobs"):
+                raise TypeError("freeze(): %d chained layers, prifit_pack_bf16_multi takes %d"
+                                % (len(self._bf16), query("prifit_pack_bf16_max_jobs")))
+            off16 = 0
+            for w in self._bf16:
+                w.off, off16 = off16, off16 + (w.cout * w.ldk + _ALIGN16 - 1) // _ALIGN16 * _ALIGN16
+            self.register_buffer("flat_bf16", torch.zeros(off16, dtype=torch.int16, device=dev))
         self._bound = None
         nn.Module.train(self, False)
         self.refresh()
@@ -168,7 +210,8 @@ class FrozenPartSeg(nn.Module):
     def _bind(self):
         """Views of the flat buffer for every consumer (again after the module moved: `.to()` replaces the parameter's storage)."""
         flat = self.flat.data
-        if self._bound == (flat.data_ptr(), flat.device):
+        key = (flat.data_ptr(), flat.device) + ((self.flat_bf16.data_ptr(), self.flat_bf16.device) if self._bf16 else ())
+        if self._bound == key:
             return flat
         for ly in self._layers:
             ly.W = flat[ly.w_off:ly.w_off + ly.cout * ly.ldw].view(ly.cout, ly.ldw)
@@ -177,13 +220,16 @@ class FrozenPartSeg(nn.Module):
             p.W = flat[p.off:p.off + p.layer.cout * len(p.cols)].view(p.layer.cout, len(p.cols))
         self._ones = flat[self._ones_off:self._ones_off + self._unit_c]
         self._zeros = flat[self._zeros_off:self._zeros_off + self._unit_c]
-        self._bound = (flat.data_ptr(), flat.device)
+        for w in self._bf16:
+            w.W = self.flat_bf16[w.off:w.off + w.cout * w.ldk].view(w.cout, w.ldk)
+        self._bound = key
         return flat
 
     @torch.no_grad()
     def refresh(self):
         """Fold the live model's current weights and statistics into the flat buffer: one fold launch for every layer, one
-        pack launch for the column-permuted first-layer weights."""
+        pack launch for the column-permuted first-layer weights; with precision="bf16" one more launch that writes every
+        chained layer's bf16 weight from them."""
         flat = self._bind()
         ls = self._layers
         n = len(ls)
@@ -218,6 +264,14 @@ class FrozenPartSeg(nn.Module):
                  (ctypes.c_int32 * m)(*[p.layer.cout for p in ps]), (ctypes.c_int32 * m)(*[p.layer.ldw for p in ps]),
                  nn_ops._ptr_array(maps), (ctypes.c_int32 * m)(*[len(p.cols) for p in ps]), nn_ops._ptr_array([p.W for p in ps]),
                  cur_stream())
+        if self._bf16:
+            ws = self._bf16
+            m = len(ws)
+            if self.flat_bf16.device != flat.device:
+                raise RuntimeError("refresh(): flat is on %s, flat_bf16 on %s" % (flat.device, self.flat_bf16.device))
+            call("prifit_pack_bf16_multi", m, nn_ops._ptr_array([w.src.W for w in ws]), (ctypes.c_int32 * m)(*[w.cout for w in ws]),
+                 (ctypes.c_int32 * m)(*[w.cols for w in ws]), (ctypes.c_int32 * m)(*[w.src.W.stride(0) for w in ws]),
+                 (ctypes.c_int32 * m)(*[w.order for w in ws]), nn_ops._ptr_array([w.W for w in ws]), cur_stream())
         return self
 
     # ------------------------------------------------------------------ the forward
@@ -273,13 +327,15 @@ class FrozenPartSeg(nn.Module):
         return outs
 
     def _tail_shape(self):
-        """(K0, widths) of the per-point tail; NotImplementedError where prifit_mlp_chain_rows_f32 does not take it."""
+        """(K0, widths) of the per-point tail; NotImplementedError where the row chain of this precision does not take it."""
         K0, widths = self._tail_kp, [ly.cout for ly in self._tail]
         L = len(widths)
-        if not dll().prifit_mlp_chain_rows_supported(K0, L, (ctypes.c_int32 * L)(*widths)):
+        entry, asks = (("prifit_mlp_chain_rows_bf16", "prifit_mlp_chain_rows_bf16_supported") if self._bf16 else
+                       ("prifit_mlp_chain_rows_f32", "prifit_mlp_chain_rows_supported"))
+        if not getattr(dll(), asks)(K0, L, (ctypes.c_int32 * L)(*widths)):
             raise NotImplementedError("FrozenPartSeg.labels(): a tail of %d input columns and widths %s is outside "
-                                      "prifit_mlp_chain_rows_f32 (4 layers, 128 / 128 / 128 / at most 64 parts, at most 160 "
-                                      "columns); there is no fall-back" % (K0, tuple(widths)))
+                                      "%s (4 layers, 128 / 128 / 128 / at most 64 parts, at most 160 "
+                                      "columns); there is no fall-back" % (K0, tuple(widths), entry))
         return K0, widths
 
     def labels(self, xyz, cls_label, shape_cat=None, cat_of_label=None, fps_start=None, return_scores=False):
@@ -314,12 +370,16 @@ class FrozenPartSeg(nn.Module):
             P, L = B * N, len(widths)
             out = torch.empty(B, N, dtype=torch.int32, device=dev)
             scores = torch.empty(B, N, parts, dtype=torch.float32, device=dev) if return_scores else None
-            Ws = [self._tail_w0.W] + [ly.W for ly in self._tail[1:]]
-            nws = dll().prifit_mlp_chain_rows_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
+            if self._bf16:
+                entry, Ws = "prifit_mlp_chain_rows_bf16", [w.W for w in self._tail_bf16]
+                nws = dll().prifit_mlp_chain_rows_bf16_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
+            else:
+                entry, Ws = "prifit_mlp_chain_rows_f32", [self._tail_w0.W] + [ly.W for ly in self._tail[1:]]
+                nws = dll().prifit_mlp_chain_rows_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
             ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
             flops = 2.0 * P * sum(k * c for k, c in zip([K0] + widths[:-1], widths))
-            with profiler.span(profiler.tag("mlp_chain_rows", P, K0, *widths), flops):
-                call("prifit_mlp_chain_rows_f32", ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths),
+            with profiler.span(profiler.tag("mlp_chain_rows_bf16" if self._bf16 else "mlp_chain_rows", P, K0, *widths), flops):
+                call(entry, ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths),
                      nn_ops._ptr_array(Ws), (ctypes.c_longlong * L)(*[W.stride(0) for W in Ws]),
                      nn_ops._ptr_array([ly.b for ly in self._tail]), ptr(scores), _LL(parts), ptr(out), ptr(cat_of_label),
                      ptr(shape_cat), N, ptr(ws), cur_stream())
@@ -405,11 +465,22 @@ class FrozenPartSeg(nn.Module):
         outw = [st[-1].cout for st, _ in scales]
         wide = torch.empty(B * S, sum(outw), dtype=torch.float32, device=dev)
         c0 = 0
-        for (st, _), K, Y, C2 in zip(scales, nsamples, Ys, outw):
+        for si, ((st, _), K, Y, C2) in enumerate(zip(scales, nsamples, Ys, outw)):
             win = wide[:, c0:c0 + C2]
             c0 += C2
             C0, C1 = st[0].cout, st[1].cout
-            if query("prifit_mlp_chain_pool_supported", C0, C1, C2, K):
+            if self._bf16:
+                if not query("prifit_mlp_chain_pool_bf16_supported", C0, C1, C2, K):
+                    raise NotImplementedError("FrozenPartSeg(precision='bf16'): a scale of widths (%d, %d, %d) over %d samples is "
+                                              "outside prifit_mlp_chain_pool_bf16; there is no fall-back" % (C0, C1, C2, K))
+                G = B * S
+                w1, w2 = lv["bf16"][si]
+                nws = query("prifit_mlp_chain_pool_bf16_workspace", G, K, C0, C1, C2)
+                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
+                with profiler.span(profiler.tag("mlp_chain_pool_bf16", G * K, C0, C1, C2), 2.0 * G * K * (C0 * C1 + C1 * C2)):
+                    call("prifit_mlp_chain_pool_bf16", ptr(Y), _LL(C0), G, K, C0, C1, C2, ptr(w1.W), _LL(w1.ldk), ptr(st[1].b),
+                         ptr(w2.W), _LL(w2.ldk), ptr(st[2].b), ptr(win), _LL(wide.stride(0)), ptr(ws), cur_stream())
+            elif query("prifit_mlp_chain_pool_supported", C0, C1, C2, K):
                 G = B * S
                 nws = query("prifit_mlp_chain_pool_workspace", G, K, C0, C1, C2)
                 ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
@@ -443,7 +514,8 @@ class FrozenPartSeg(nn.Module):
         return rows
 
 
-def freeze(model):
+def freeze(model, precision="fp32"):
     """A FrozenPartSeg of `model` (a models.pointnet2_part_seg_msg.get_model on the GPU, reconstruct=False); TypeError for
-    every other network."""
-    return FrozenPartSeg(model)
+    every other network.  precision: "fp32" or "bf16" (the on-chip chains in bf16 with fp32 accumulation, DESIGN.md 3.9.2);
+    ValueError for anything else."""
+    return FrozenPartSeg(model, precision)
