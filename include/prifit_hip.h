@@ -301,7 +301,7 @@ int prifit_gemm_stream_tn_pool_f32(int Mo, int No, long long P, const float *Y, 
  * A[row,0:No] with A read as max(a*b_scale[n]+b_shift[n], 0) when the prologue is given.  `out` is initialised by
  * the caller (zeros, or a gradient to accumulate into).  Every wave streams its own rows as MFMA fragments (no
  * LDS staging); per-workgroup partial slabs go to `workspace` (prifit_gemm_stream_tn_workspace(Mo,No,P) floats,
- * caller-owned scratch) and a second small launch adds them to `out`. */
+ * caller-owned scratch) and two small launches add them to `out` in a fixed order: deterministic, no atomics. */
 /* The same two streaming products for a MIDDLE layer of a shared MLP (autograd of models/pointnet_util.py:195-199 /
  * :252-256): the layer's dY = a*(Y*scale+shift > 0 ? G : 0) + b*Y + d -- prifit_bn_relu_bwd_apply's expression with
  * the coefficients of prifit_bn_bwd_finalize -- is formed from G (gradient w.r.t. relu(bn(Y)), leading dimension ldy)

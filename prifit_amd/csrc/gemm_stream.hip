@@ -306,14 +306,17 @@ __global__ __launch_bounds__(256, (KG <= 8 ? ((RED || PMAX || POOL) ? 3 : 4) : (
             for (int a = 0; a < TM; ++a) {
                 float vmax = -INFINITY, vmin = INFINITY;
                 int imax = 0, imin = 0;
+                // the 16 rows of an accumulator tile are summed on their own and then added to the running sums: one chain over
+                // the 32 rows of a TM = 2 wave rounds a run of equal rows (a padded ball) 32 times the same way
+                float ts = 0.f, tq = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = m0 + 32 * a + (r & 3) + 8 * (r >> 2);
                     const bool rok = full || row < g.M;   // (tail tile only; its stores are dropped by the bounds check)
                     const float v = acc[a][r] + bias;
                     const float vs = rok ? v : 0.f;
-                    csum += vs;
-                    csq += vs * vs;
+                    ts += vs;
+                    tq += vs * vs;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), crs, c_voff,
                                                           (32 * a + (r & 3) + 8 * (r >> 2)) * ldc4, 0);
                     if (PMAX) {  // rows ascend with r inside a lane: strict comparisons keep the first occurrence
@@ -328,6 +331,8 @@ __global__ __launch_bounds__(256, (KG <= 8 ? ((RED || PMAX || POOL) ? 3 : 4) : (
                         m2 += gm * ((y - r_mu) * r_is);
                     }
                 }
+                csum += ts;
+                csq += tq;
                 if (PMAX) {
                     // the other half of the block's rows lives in lane ^ 32; ties go to the lower row
                     const float ov = __shfl_xor(vmax, 32, 64), on = __shfl_xor(vmin, 32, 64);
@@ -641,25 +646,46 @@ __global__ __launch_bounds__(256, OCC) void gemm_stream_tn_kernel(const StreamTN
     }
 }
 
-// out[m, n] += sum over slabs of ws[slab][m * No + n]; gridDim.y slices of the slab range (32 adders per address), four
-// independent partial sums per thread so that the slab loads of a slice are in flight together
-__global__ __launch_bounds__(256) void stream_tn_reduce_kernel(const float *__restrict__ ws, int nslab, int Mo, int No,
-                                                               long long ldo, float *__restrict__ out)
+// out[m, n] += sum over slabs of ws[slab][m * No + n], in a fixed order (the same bits from run to run): gridDim.y slices
+// of the slab range, four independent partial sums per thread so that the slab loads of a slice are in flight together; a
+// slice leaves its sum in the place of its first slab (element e of a slice's slabs is read and written by one thread only),
+// and stream_tn_add_kernel adds the slices' sums to `out` one after the other.  (The slices used to add to `out` with float
+// atomics, in arrival order: two runs differed in the last bits.)
+__global__ __launch_bounds__(256) void stream_tn_reduce_kernel(float *__restrict__ ws, int nslab, int Mo, int No)
 {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Mo * No) return;
     const int per = (nslab + gridDim.y - 1) / gridDim.y;
     const int s0 = blockIdx.y * per, s1 = min(nslab, s0 + per);
+    if (s1 <= s0) return;
     const long long stride = (long long)Mo * No;
-    const float *p = ws + (long long)s0 * stride + e;
+    float *p0 = ws + (long long)s0 * stride + e;
+    const float *p = p0;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
     int sl = s0;
     for (; sl + 4 <= s1; sl += 4, p += 4 * stride) {
         a0 += p[0]; a1 += p[stride]; a2 += p[2 * stride]; a3 += p[3 * stride];
     }
     for (; sl < s1; ++sl, p += stride) a0 += p[0];
+    *p0 = (a0 + a1) + (a2 + a3);
+}
+
+__global__ __launch_bounds__(256) void stream_tn_add_kernel(const float *__restrict__ ws, int nslab, int nslice, int Mo, int No,
+                                                            long long ldo, float *__restrict__ out)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= Mo * No) return;
+    const int per = (nslab + nslice - 1) / nslice;
+    const long long stride = (long long)Mo * No * per;
+    const float *p = ws + e;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int y = 0;
+    for (; y + 4 <= nslice && (y + 3) * per < nslab; y += 4, p += 4 * stride) {
+        a0 += p[0]; a1 += p[stride]; a2 += p[2 * stride]; a3 += p[3 * stride];
+    }
+    for (; y < nslice && y * per < nslab; ++y, p += stride) a0 += p[0];
     const int m = e / No, n = e - m * No;
-    if (s1 > s0) unsafeAtomicAdd(out + (long long)m * ldo + n, (a0 + a1) + (a2 + a3));
+    out[(long long)m * ldo + n] += (a0 + a1) + (a2 + a3);
 }
 
 int stream_grid(int M, int K)
@@ -782,8 +808,11 @@ static int stream_tn_launch(StreamTNArgs &g, float *out, long long ldo, void *st
     else if (p.am == 2) stream_tn_launch_pf<2, 1>(g, p, grid, st);
     else if (p.an == 2) stream_tn_launch_pf<1, 2>(g, p, grid, st);
     else stream_tn_launch_pf<1, 1>(g, p, grid, st);
-    hipLaunchKernelGGL(stream_tn_reduce_kernel, dim3((g.Mo * g.No + 255) / 256, nwg < 32 ? (unsigned)nwg : 32u), dim3(256), 0, st,
-                       g.ws, (int)nwg, g.Mo, g.No, ldo, out);
+    const int nslice = nwg < 32 ? (int)nwg : 32;
+    hipLaunchKernelGGL(stream_tn_reduce_kernel, dim3((g.Mo * g.No + 255) / 256, (unsigned)nslice), dim3(256), 0, st, g.ws, (int)nwg,
+                       g.Mo, g.No);
+    hipLaunchKernelGGL(stream_tn_add_kernel, dim3((g.Mo * g.No + 255) / 256), dim3(256), 0, st, g.ws, (int)nwg, nslice, g.Mo, g.No,
+                       ldo, out);
     return prifit_check_launch();
 }
 

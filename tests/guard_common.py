@@ -111,3 +111,71 @@ def assert_guards_intact(base, view, poison=SENTINEL):
         first = int(bad.nonzero()[0])
         raise AssertionError("%d guard word(s) overwritten; first at float %d of the buffer (view: floats %d ..): 0x%08x"
                              % (n, first, view.storage_offset() - base.storage_offset(), int(bits[first]) & 0xffffffff))
+
+
+BUFS_LEAD = 4096
+BUFS_TAIL = 129 * 1056      # 129 rows of the widest leading dimension the norm / pool / gather cases use (1028 + 28)
+
+
+class Bufs:
+    """Guarded buffers of one case: *in = inputs in NaN guards, *out = outputs in SENTINEL guards; `lead` / `tail` floats of
+    guard in front of and behind every one of them."""
+
+    def __init__(self, lead=BUFS_LEAD, tail=BUFS_TAIL, device="cuda"):
+        self.items = []
+        self.lead, self.tail, self.device = lead, tail, device
+
+    def _guarded(self, shape, poison):
+        v, base = guarded(tuple(shape), self.lead, self.tail, poison, self.device)
+        self.items.append((base, v, poison))
+        return v
+
+    def _mat(self, P, C, ld, poison):
+        v, base = guarded_matrix(P, C, ld, self.lead, self.tail, poison, self.device)
+        self.items.append((base, v, poison))
+        return v
+
+    def fin(self, t, ld=None):
+        t = t.detach().to(torch.float32)
+        v = self._guarded(t.shape, float("nan")) if ld is None else self._mat(t.shape[0], t.shape[1], ld, float("nan"))
+        v.copy_(t)
+        return v
+
+    def iin(self, t, poison):
+        """int32 input; `poison` is an IN-RANGE value whose use shows in the results (a NaN's bit pattern read as an index is
+        out of range everywhere, and the kernels drop such an index silently)"""
+        v = self._guarded(t.shape, int(poison))
+        v.view(torch.int32).copy_(t.to(torch.int32))
+        return v.view(torch.int32)
+
+    def din(self, t):
+        v = self._guarded(tuple(t.shape[:-1]) + (2 * t.shape[-1],), float("nan"))
+        v.view(torch.float64).copy_(t.to(torch.float64))
+        return v.view(torch.float64)
+
+    def fout(self, shape, zero=False, init=None):
+        v = self._guarded(shape, SENTINEL)
+        if zero:
+            v.zero_()
+        if init is not None:
+            v.copy_(init)
+        return v
+
+    def mout(self, P, C, ld, col0=0, wide=None):
+        """[P, C] output at column col0 of a [P, wide] matrix with row stride ld: the other columns are guards too"""
+        m, base = guarded_matrix(P, wide or C, ld, self.lead, self.tail, SENTINEL, self.device)
+        v = m[:, col0:col0 + C]
+        self.items.append((base, v, SENTINEL))
+        return v
+
+    def iout(self, shape):
+        return self.fout(shape).view(torch.int32)
+
+    def dout(self, shape):
+        return self.fout(tuple(shape[:-1]) + (2 * shape[-1],)).view(torch.float64)
+
+    def intact(self):
+        if self.device != "cpu":
+            torch.cuda.synchronize()
+        for base, v, poison in self.items:
+            assert_guards_intact(base, v, poison)

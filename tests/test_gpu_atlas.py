@@ -293,7 +293,10 @@ def _sha(t):
 
 def test_model_without_reconstruct_matches_recorded_bits(hiplib, golden):
     """seg and feat of the reconstruct=False net at the seeded whole-model case, against SHA-256 digests recorded on an MI355X
-    from the revision before reconstruct=True existed (tests/golden/atlas_model_digest.npz)"""
+    (tests/golden/atlas_model_digest.npz).  First recorded from the revision before reconstruct=True existed; recorded again,
+    by this test's own recipe, when the streaming forward began to sum its column statistics per accumulator tile (DESIGN.md,
+    the streaming kernels' tests): the library before that change still gives the first digests, the one after it gives
+    these in two separate processes."""
     G = golden("atlas_model_digest")
     xyz, cls = ac.model_inputs()
     a = _model(False)

@@ -129,14 +129,12 @@ import torch
 
 import bn_common as bc
 from bn_common import F32, F64
-from guard_common import SENTINEL, assert_guards_intact, guarded, guarded_matrix
+from guard_common import Bufs
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
 LL = ctypes.c_longlong
-LEAD = 4096
-TAIL = 129 * 1056       # 129 rows of the widest leading dimension any case uses (1028 + 28)
 
 
 @pytest.fixture(scope="module")
@@ -144,69 +142,6 @@ def A(hiplib):
     assert torch.cuda.is_available()
     from prifit_amd import _lib
     return _lib
-
-
-class Bufs:
-    """Guarded buffers of one case: *in = inputs in NaN guards, *out = outputs in SENTINEL guards."""
-
-    def __init__(self):
-        self.items = []
-
-    def _mat(self, P, C, ld, poison):
-        v, base = guarded_matrix(P, C, ld, LEAD, TAIL, poison)
-        self.items.append((base, v, poison))
-        return v
-
-    def fin(self, t, ld=None):
-        t = t.detach().to(F32)
-        if ld is None:
-            v, base = guarded(tuple(t.shape), LEAD, TAIL, NAN)
-            self.items.append((base, v, NAN))
-        else:
-            v = self._mat(t.shape[0], t.shape[1], ld, NAN)
-        v.copy_(t)
-        return v
-
-    def iin(self, t, poison):
-        """int32 input; `poison` is an IN-RANGE value whose use shows in the results (a NaN's bit pattern read as an index is
-        out of range everywhere, and the kernels drop such an index silently)"""
-        v, base = guarded(tuple(t.shape), LEAD, TAIL, int(poison))
-        v.view(torch.int32).copy_(t.to(torch.int32))
-        self.items.append((base, v, int(poison)))
-        return v.view(torch.int32)
-
-    def din(self, t):
-        v, base = guarded(tuple(t.shape[:-1]) + (2 * t.shape[-1],), LEAD, TAIL, NAN)
-        v.view(F64).copy_(t.to(F64))
-        self.items.append((base, v, NAN))
-        return v.view(F64)
-
-    def fout(self, shape, zero=False, init=None):
-        v, base = guarded(tuple(shape), LEAD, TAIL, SENTINEL)
-        if zero:
-            v.zero_()
-        if init is not None:
-            v.copy_(init)
-        self.items.append((base, v, SENTINEL))
-        return v
-
-    def mout(self, P, C, ld, col0=0, wide=None):
-        """[P, C] output at column col0 of a [P, wide] matrix with row stride ld: the other columns are guards too"""
-        m, base = guarded_matrix(P, wide or C, ld, LEAD, TAIL, SENTINEL)
-        v = m[:, col0:col0 + C]
-        self.items.append((base, v, SENTINEL))
-        return v
-
-    def iout(self, shape):
-        return self.fout(shape).view(torch.int32)
-
-    def dout(self, shape):
-        return self.fout(tuple(shape[:-1]) + (2 * shape[-1],)).view(F64)
-
-    def intact(self):
-        torch.cuda.synchronize()
-        for base, v, poison in self.items:
-            assert_guards_intact(base, v, poison)
 
 
 def finite(*ts):

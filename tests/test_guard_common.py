@@ -4,7 +4,7 @@ import math
 import pytest
 import torch
 
-from guard_common import (ALIGN, SENTINEL, assert_guards_intact, guarded, guarded_like, guarded_matrix, padded_stream, poison_bits, x_tail)
+from guard_common import (ALIGN, BUFS_LEAD, BUFS_TAIL, SENTINEL, Bufs, assert_guards_intact, guarded, guarded_like, guarded_matrix, padded_stream, poison_bits, x_tail)
 
 
 def test_guarded_view_alignment_contiguity_and_poison():
@@ -98,3 +98,37 @@ def test_guarded_matrix_layout():
                 assert_guards_intact(base, m)
     with pytest.raises(AssertionError):
         guarded_matrix(4, 8, 7, 0, 0, device="cpu")
+
+
+def test_bufs_put_every_tensor_in_guards_of_the_asked_size_and_see_one_word():
+    for lead, tail in ((BUFS_LEAD, BUFS_TAIL), (64 * 152, 128 * 152)):
+        g = Bufs(lead, tail, device="cpu")
+        t = torch.arange(15, dtype=torch.float32).view(5, 3)
+        a, b = g.fin(t), g.fin(t, ld=7)
+        ix = g.iin(torch.tensor([3, 1, 2]), 9)
+        d = g.din(torch.ones(2, 3, dtype=torch.float64))
+        o, m = g.fout((4, 3)), g.mout(5, 3, 12, col0=4, wide=8)
+        z, i, dd = g.fout((2,), zero=True), g.iout((3,)), g.dout((2, 2))
+        assert torch.equal(a, t) and torch.equal(b, t) and b.stride() == (7, 1) and m.stride() == (12, 1)
+        assert ix.dtype == torch.int32 and ix.tolist() == [3, 1, 2] and d.dtype == torch.float64 and bool((d == 1).all())
+        assert i.dtype == torch.int32 and dd.dtype == torch.float64 and dd.shape == (2, 2) and not bool(z.any())
+        assert len(g.items) == 9
+        for base, v, poison in g.items:
+            s = v.storage_offset() - base.storage_offset()
+            assert s >= lead and (v.data_ptr() % ALIGN == 0 or v.data_ptr() == m.data_ptr())
+            last = s + sum((n - 1) * st for n, st in zip(v.shape, v.stride()))
+            assert base.numel() - 1 - last >= tail
+        assert (o.view(torch.int32) == SENTINEL).all()          # outputs hold the sentinel until written
+        pads = [x for x in g.items if x[1].data_ptr() == b.data_ptr()][0][0]
+        assert int(torch.isnan(pads).sum()) == pads.numel() - 15        # the pad columns of an input are NaN
+        guards = [x for x in g.items if x[1].data_ptr() == ix.data_ptr()][0][0]
+        assert int((guards.view(torch.int32) == 9).sum()) == guards.numel() - 3      # the in-range index poison
+        g.intact()
+        o.zero_()
+        m.zero_()
+        g.intact()                                               # the views themselves are not guards
+        base = [x for x in g.items if x[1].data_ptr() == m.data_ptr()][0][0]
+        at = m.storage_offset() - base.storage_offset() + 3      # the column behind the slice, first row
+        base.view(torch.int32)[at] = 0
+        with pytest.raises(AssertionError, match="1 guard word"):
+            g.intact()
