@@ -109,6 +109,13 @@ __global__ __launch_bounds__(256) void edge_csr_fill_kernel(const int32_t *__res
     }
 }
 
+template <int N>
+__device__ __forceinline__ float tree_sum(const float *a)
+{
+    if constexpr (N == 1) return a[0];
+    else return tree_sum<N / 2>(a) + tree_sum<N - N / 2>(a + N / 2);
+}
+
 // ---- forward pass over the neighbour lists: one wave per point, lane = channels lane, lane + 64, ... ----
 template <int V, int UNR>
 __global__ __launch_bounds__(256) void edge_stats_kernel(const float *__restrict__ U, long long ldu,
@@ -132,14 +139,17 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float *__restrict
     for (int p = p0 + wave; p < p_end; p += 4) {
         const size_t g = (size_t)b * N + p;
         const int32_t *ix = idx + g * k;
-        float vc[V], s[V], mx[V], mn[V];
+        // sums over the neighbours: a pairwise tree over the UNR slots of a batch, then one chain over the k / UNR batches of the
+        // point (one chain of k additions, and of 4 k for the squares, left the bars of tests/test_gpu_dgcnn_graph_guards.py
+        // behind from k = 20 on; the tree lives in the batch's own registers)
+        float vc[V], s[V], q[V], mx[V], mn[V];
         int kx[V], kn[V], nv = 0;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             vc[v] = Vc[g * ldv + lane + 64 * v];
             if (selfterm) vc[v] = U[g * ldu + lane + 64 * v] - vc[v];     // centre term U_i - Vb_i (see prifit_edge_stats)
             vct[g * C + lane + 64 * v] = vc[v];
-            s[v] = 0.f; mx[v] = -INFINITY; mn[v] = INFINITY; kx[v] = 0; kn[v] = 0;
+            s[v] = 0.f; q[v] = 0.f; mx[v] = -INFINITY; mn[v] = INFINITY; kx[v] = 0; kn[v] = 0;
         }
         for (int kc = 0; kc < k; kc += 64) {                  // the index list sits in the lanes: no load between two row gathers
             const int kn_here = min(64, k - kc);
@@ -157,17 +167,23 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float *__restrict
                 }
 #pragma unroll
                 for (int j = 0; j < UNR; ++j) {
-                    if (kk + j < kn_here) {
-                        nv += ok[j] ? 1 : 0;
+                    const bool live = kk + j < kn_here;     // wave-uniform
+                    nv += live && ok[j] ? 1 : 0;
 #pragma unroll
-                        for (int v = 0; v < V; ++v) {
-                            const float y = ok[j] ? u[j][v] - vc[v] : 0.f;
-                            s[v] += y;
-                            wq[v] = fmaf(y, y, wq[v]);
-                            if (y > mx[v]) { mx[v] = y; kx[v] = kc + kk + j; }    // strict: the first maximum / minimum
-                            if (y < mn[v]) { mn[v] = y; kn[v] = kc + kk + j; }
-                        }
+                    for (int v = 0; v < V; ++v) {
+                        const float y = ok[j] ? u[j][v] - vc[v] : 0.f;
+                        u[j][v] = y;                        // (a dead slot has ok = false: y = 0)
+                        if (live && y > mx[v]) { mx[v] = y; kx[v] = kc + kk + j; }    // strict: the first maximum / minimum
+                        if (live && y < mn[v]) { mn[v] = y; kn[v] = kc + kk + j; }
                     }
+                }
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    float ts[UNR], tq[UNR];
+#pragma unroll
+                    for (int j = 0; j < UNR; ++j) { ts[j] = u[j][v]; tq[j] = u[j][v] * u[j][v]; }
+                    s[v] += tree_sum<UNR>(ts);
+                    q[v] += tree_sum<UNR>(tq);
                 }
             }
         }
@@ -176,6 +192,7 @@ __global__ __launch_bounds__(256) void edge_stats_kernel(const float *__restrict
             const size_t o = g * C + lane + 64 * v;
             ymax[o] = mx[v]; ymin[o] = mn[v]; karg[o] = kx[v] | (kn[v] << 10) | (nv << 20); ysum[o] = s[v];
             ws[v] += s[v];
+            wq[v] += q[v];
         }
     }
 #pragma unroll
@@ -240,7 +257,10 @@ __global__ __launch_bounds__(256) void edge_bwd_point_kernel(const float *__rest
             const float T = ca[to] * act_grad(fmaf(ystar[id], s, t), gp[g * ldgp + c], slope);
             const int pk = karg[id];
             const int w = s < 0.f ? ((pk >> 10) & 1023) : (pk & 1023);
-            const int n = w < 64 ? __shfl(nl, w, 64) : ix[w];
+            // (the shuffle outside the select: inside it, the lanes whose own winner sits at w >= 64 are switched off while it
+            // runs, and a lane that reads one of them gets 0 -- an in-range index -- where the entry is out of range)
+            const int nsh = __shfl(nl, w & 63, 64);
+            const int n = w < 64 ? nsh : ix[w];
             // a zero row (index out of range) is a constant: it takes part in the statistics, not in the gradients
             const bool ok = n >= 0 && n < N;
             aT[id] = T;
