@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 802
+#define PRIFIT_ABI_VERSION 803
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -995,6 +995,31 @@ int prifit_sgd_flat(float *params, float *momentum_buf, const float *const *grad
  * n_subset <= 0; dst_cf == src; src or affine NULL. */
 int prifit_affine_points(const float *src, int B, int M, int C, const float *affine, const int32_t *subset, int n_subset,
                          float *dst_cl, float *dst_cf, float *dst_sub, void *stream);
+/* The per-point augmentations on top of that map, in one launch: the normals of an xyz + normal batch rotated with the points
+ * (provider.py:150-194, :216-236), clipped Gaussian jitter (:265-276) and random point dropout (:320-327).
+ * src [B, M, C] channels-last, C == 3 (xyz) or C == 6 (xyz, normal).  Per point p of shape b, in this order:
+ *   1. affine [B, 12] (A row-major, then t), or NULL: xyz = the expression of prifit_affine_points, the same bits; NULL = bit copies.
+ *   2. rotate_normals != 0 (needs C == 6 and affine): n'_j = (n0*A[0][j] + n1*A[1][j]) + n2*A[2][j], fp32, no fused multiply-add,
+ *      no translation; otherwise channels 3..5 are bit copies.
+ *   3. sigma > 0: xyz_k += min(max(sigma * z_k, -clip), clip), k = 0..2, every operation rounded once.  The z_k come from
+ *      (w0, w1, w2, w3) = Philox4x32-10(counter = (p, b, 0, 0), key = (seed_lo, seed_hi)) by Box-Muller on 24-bit uniforms:
+ *        u1(w) = ((w >> 8) + 1) * 2^-24 in (0, 1],  u2(w) = (w >> 8) * 2^-24 in [0, 1)   (both exact in fp32),
+ *        r(w) = sqrtf(-2 * logf(u1(w))),  th(w) = fp32(2 pi) * u2(w)   (fp32(2 pi) = 0x40C90FDB),
+ *        z0 = r(w0) * cosf(th(w1)),  z1 = r(w0) * sinf(th(w1)),  z2 = r(w2) * cosf(th(w3)).
+ *      sigma == 0: no jitter, clip is not looked at.
+ *   4. drop_ratio [B] (device) or NULL: point p is dropped iff u2(v0) <= drop_ratio[b] (an exact fp32 comparison), v0 the first
+ *      word of Philox4x32-10(counter = (p, b, 1, 0), same key).  A dropped point takes all C output channels of point 0 of its
+ *      shape as steps 1-3 leave them (upstream writes the first point over the dropped ones); point 0 may itself be dropped,
+ *      which leaves it as it is.
+ * dst_cl [B, M, C] channels-last (may be == src: in place) and dst_cf [B, C, M] channels-first hold the same bits; each is
+ * optional (NULL), at least one must be given.  The generator has no state and nothing is accumulated: one seed gives the
+ * same bits in every run and for every launch geometry; jitter and dropout use different streams (counter word 2) of one seed.
+ * A workgroup forms point 0's output itself from point 0's source, so none waits for another; in place with dropout one
+ * workgroup takes a whole shape (it reads point 0 before it writes), which costs parallelism: out of place is the fast form.
+ * PRIFIT_EINVAL without a launch: src NULL; B, M <= 0 (or B > 65535); C not 3 or 6; both outputs NULL; dst_cf == src or == dst_cl;
+ * rotate_normals with C != 6 or without affine; sigma < 0 or NaN; sigma > 0 with clip <= 0 or NaN. */
+int prifit_perturb_points(const float *src, int B, int M, int C, const float *affine, int rotate_normals, float sigma, float clip,
+                          const float *drop_ratio, uint32_t seed_lo, uint32_t seed_hi, float *dst_cl, float *dst_cf, void *stream);
 
 /* ---- part-segmentation metrics of testing.py:139-204 in one launch: the category-restricted arg-max of every point and the
  * integer counts behind accuracy, class-average accuracy and the per-shape IoU.  One pass over the scores, integer atomics

@@ -38,6 +38,7 @@ SOURCES = {
     "atlas.hip": [],
     "optim.hip": [],
     "augment.hip": ["-ffp-contract=off"],
+    "perturb.hip": ["-ffp-contract=off"],
     "seg_metrics.hip": [],
     "infer.hip": [],
     "infer_bf16.hip": [],

@@ -256,6 +256,63 @@ def affine_points(src, affine, subset=None, want_cl=False, want_cf=False, out_cl
     return cl, cfirst, sub
 
 
+def perturb_points(src, affine=None, *, rotate_normals=False, sigma=0.0, clip=0.0, drop_ratio=None, seed=0, want_cf=False, out=None):
+    """The per-point augmentations of provider.py in ONE launch (csrc/perturb.hip; contract: prifit_perturb_points in the header):
+    the per-shape map of `affine_points` on xyz, with `rotate_normals` its 3x3 part on channels 3..5 too, then clipped Gaussian
+    jitter (sigma > 0: xyz += clamp(sigma * z, -clip, clip)), then point dropout (point p of shape b takes point 0's output iff
+    its uniform draw is <= drop_ratio[b]).  src [B,M,C] contiguous float32, C 3 or 6; affine [B,12] float32 or None (xyz copied);
+    drop_ratio [B] or None; both on the host (uploaded TOGETHER in one copy) or on the device.  seed: a 64-bit integer, the key
+    of the counter-based generator -- the same seed gives the same bits.
+    -> (cl [B,M,C] | None, cf [B,C,M] | None).  cl is written into `out` when given (may be `src`: in place), else into a new
+    tensor; with want_cf and no `out`, only the channels-first copy is made and cl is None."""
+    if not torch.is_tensor(src) or src.dtype != torch.float32 or src.dim() != 3 or src.shape[2] not in (3, 6) or not src.is_contiguous():
+        raise ValueError("perturb_points: src must be a contiguous float32 [B,M,3] or [B,M,6] tensor")
+    B, M, C = src.shape
+    if B < 1 or M < 1:
+        raise ValueError("perturb_points: empty batch %s" % (tuple(src.shape),))
+    if rotate_normals and (C != 6 or affine is None):
+        raise ValueError("perturb_points: rotate_normals needs a [B,M,6] batch and an affine map")
+    sigma, clip = float(sigma), float(clip)
+    if not sigma >= 0.0 or (sigma > 0.0 and not clip > 0.0):
+        raise ValueError("perturb_points: sigma must be >= 0, and clip > 0 where sigma > 0 (got sigma %r, clip %r)" % (sigma, clip))
+    if out is not None and (not torch.is_tensor(out) or out.shape != src.shape or out.dtype != torch.float32
+                            or out.device != src.device or not out.is_contiguous()):
+        raise ValueError("perturb_points: out must be a contiguous float32 tensor of src's shape on src's device")
+    host = {}
+    for name, v, n in (("affine", affine, B * 12), ("drop_ratio", drop_ratio, B)):
+        if v is None:
+            continue
+        if torch.is_tensor(v) and v.is_cuda:
+            if v.dtype != torch.float32 or v.numel() != n or not v.is_contiguous():
+                raise ValueError("perturb_points: a device %s must hold %d contiguous float32" % (name, n))
+        else:
+            v = np.ascontiguousarray(v.numpy() if torch.is_tensor(v) else v, dtype=np.float32)
+            if v.size != n:
+                raise ValueError("perturb_points: %s must hold %d floats, got shape %s" % (name, n, v.shape))
+            host[name] = v.reshape(-1)
+        if name == "affine":
+            affine = v
+        else:
+            drop_ratio = v
+    require_cuda(src)
+    if host:                                     # what lives on the host travels in one copy
+        up = torch.from_numpy(np.concatenate(list(host.values()))).to(src.device)
+        at = 0
+        for name, v in host.items():
+            part, at = up[at:at + v.size], at + v.size
+            if name == "affine":
+                affine = part
+            else:
+                drop_ratio = part
+    seed = int(seed) & 0xffffffffffffffff
+    cl = out if out is not None else (None if want_cf else torch.empty_like(src))
+    cfirst = torch.empty(B, C, M, dtype=torch.float32, device=src.device) if want_cf else None
+    with profiler.span("perturb_points", 4.0 * B * C * M * (1 + (cl is not None) + bool(want_cf))):
+        call("prifit_perturb_points", ptr(src), B, M, C, ptr(affine), int(bool(rotate_normals)), sigma, clip, ptr(drop_ratio),
+             seed & 0xffffffff, seed >> 32, ptr(cl), ptr(cfirst), cur_stream())
+    return cl, cfirst
+
+
 def seg_metrics(scores, target, cat_of_label, restricted=True, totals=None, out=None):
     """The part-segmentation counts of testing.py:139-204 in ONE launch, nothing read back (csrc/seg_metrics.hip).
     scores [B,N,P] float32 part scores, P <= 64 (a view with a row stride >= P is taken as it is); target [B,N] int64 labels;
