@@ -7,15 +7,10 @@
 //   mlp_chain_pool_kernel  layers 2 and 3 of a scale and its pool in one launch, the intermediates in registers
 //   mlp_chain_rows_kernel  the per-point tail (fp1, conv1 + bn1, conv2) and the restricted arg-max in one launch
 //
-// The chain kernel computes the TRANSPOSED products on v_mfma_f32_32x32x2_f32 (exact fp32, the instruction of gemm.hip and
-// gemm_stream.hip): H^T = W1' X^T and Y^T = W2' H^T, the weights as the A operand and 32 rows of the activation as the B
-// operand.  The C/D layout of that instruction gives lane (j, h) the channels 8g + 4h + 0..3 (g = 0..3) of activation row j
-// -- which is exactly what the same lane has to supply as the B operand of the next product, for a k order (8g + 4h + m
-// instead of ascending k) that the A operand follows by reading W2' at those columns.  So a wave carries its 32 rows from
-// the pre-activation it loads to the pooled maximum without LDS, without a barrier and without a shuffle; the only
-// cross-lane traffic is the max over the 32 rows at the very end (DPP) and 4 C2 floats of LDS per workgroup to combine the
-// waves of a pooling group.  The weights are read from L2 / L1 as MFMA fragments (W1' + W2' are 12 .. 300 KB per scale).
-// What follows the last product of a chain is shared with the bf16 kernels of infer_bf16.hip: infer_chain.h.
+// The two chain kernels, their argument checks and their launch ladders are written once, in infer_chain.h, over a matrix-pipe
+// policy; this file holds the fold, the fp32 policy (PipeF32: v_mfma_f32_32x32x2_f32, exact fp32, the instruction of gemm.hip
+// and gemm_stream.hip) and the fp32 entry points, which instantiate the skeleton for it.  The bf16 twin is infer_bf16.hip.
+// The weights are read from L2 / L1 as MFMA fragments (W1' + W2' are 12 .. 300 KB per scale).
 #include <algorithm>
 
 #include "infer_chain.h"
@@ -65,235 +60,38 @@ __global__ __launch_bounds__(256) void fold_bn_kernel(FoldJobs jb)
     }
 }
 
-struct ChainArgs {
-    const float *X;
-    long long ldx;
-    long long P;             // G * pool_K rows
-    int G, pool_K;
-    const float *W1, *b1, *W2, *b2;
-    long long ldw1, ldw2;
-    float *out;
-    long long ldo;
-};
-
-// X [P, C0] (pre-activation of layer 1, ReLU on load) -> out[g, :] = max over the pool_K rows of group g of
-// relu(W2 relu(W1 relu(x) + b1) + b2); W1 [C1, ldw1], W2 [C2, ldw2].  C0 % 8 == 0, C1 % 4 == 0, C2 % 32 == 0,
-// pool_K in {32, 64, 128}: a wave's 32 rows lie in one group and a workgroup's 128 rows hold whole groups.
-template <int C0, int C1, int C2>
-__global__ __launch_bounds__(256) void mlp_chain_pool_kernel(const ChainArgs g)
-{
-    static_assert(C0 % 8 == 0 && C1 % 4 == 0 && C2 % 32 == 0, "fragment shapes");
-    constexpr int KQ = C0 / 8, NB1 = (C1 + 31) / 32, NB2 = C2 / 32;
-    __shared__ __attribute__((aligned(16))) float s_pool[4][C2];
-
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int li = lane & 31, lh = lane >> 5;
-    const long long row0 = (long long)blockIdx.x * CHAIN_ROWS + 32 * wave;
-
-    if (row0 < g.P) {    // wave-uniform; P % 32 == 0: a live wave has 32 rows
-        // B operand of layer 1: lane (j, h) holds X[row0 + j][8q + 4h + 0..3], ReLU applied
-        float4 xf[KQ];
-        {
-            const float *xr = g.X + (row0 + li) * g.ldx + 4 * lh;
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const float4 v = ld4(xr + 8 * q);
-                xf[q] = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-            }
-        }
-        // layer 1: h[b][4g + m] = relu(.) of channel 32b + 8g + 4h + m of row j; channels >= C1 are exactly 0
-        f32x16 h[NB1];
-#pragma unroll
-        for (int b = 0; b < NB1; ++b) {
-            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const int c = 32 * b + li;
-            const bool ok = c < C1;
-            const float *wr = g.W1 + (long long)(ok ? c : 0) * g.ldw1 + 4 * lh;
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                float4 a = ld4(wr + 8 * q);
-                if (!ok) a = make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xf[q].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xf[q].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xf[q].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xf[q].w, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int c0 = 32 * b + 8 * gq + 4 * lh;       // C1 % 4 == 0: the four channels are in or out together
-                const float4 bb = c0 < C1 ? ld4(g.b1 + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc[4 * gq + 0] = fmaxf(acc[4 * gq + 0] + bb.x, 0.f);
-                acc[4 * gq + 1] = fmaxf(acc[4 * gq + 1] + bb.y, 0.f);
-                acc[4 * gq + 2] = fmaxf(acc[4 * gq + 2] + bb.z, 0.f);
-                acc[4 * gq + 3] = fmaxf(acc[4 * gq + 3] + bb.w, 0.f);
-            }
-            h[b] = acc;
-        }
-        // layer 2 + the max over this wave's 32 rows, 32 output channels at a time
-#pragma unroll 1
-        for (int b2 = 0; b2 < NB2; ++b2) {
-            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const float *wr = g.W2 + (long long)(32 * b2 + li) * g.ldw2;
-#pragma unroll
-            for (int b = 0; b < NB1; ++b) {
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    if (32 * b + 8 * gq >= C1) continue;                  // (compile time) no such input channels
-                    const int k0 = 32 * b + 8 * gq + 4 * lh;
-                    float4 a;
-                    if (32 * b + 8 * gq + 8 <= C1) a = ld4(wr + k0);      // (compile time) both halves inside the row
-                    else {                                                // C1 % 8 == 4: the upper half is past the row's end
-                        a = ld4(wr + (k0 < C1 ? k0 : 0));
-                        if (k0 >= C1) a = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, h[b][4 * gq + 0], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, h[b][4 * gq + 1], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, h[b][4 * gq + 2], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, h[b][4 * gq + 3], acc, 0, 0, 0);
-                }
-            }
-            chain_pool_block(acc, g.b2, b2, li, lh, s_pool[wave]);
-        }
-    }
-    __syncthreads();
-    chain_pool_groups<C2>(s_pool, g.G, g.pool_K, g.out, g.ldo);
-}
-
-template <int C0, int C1, int C2>
-void chain_launch(const ChainArgs &g, hipStream_t st)
-{
-    const unsigned grid = (unsigned)((g.P + CHAIN_ROWS - 1) / CHAIN_ROWS);
-    hipLaunchKernelGGL((mlp_chain_pool_kernel<C0, C1, C2>), dim3(grid), dim3(256), 0, st, g);
-}
-
-// ---- the per-point tail of the part-segmentation network: four layers over raw rows, scores and / or part labels out
-//
-// The layout argument above does not stop at two layers: whatever the depth, the C/D registers of one transposed product
-// are the B operand of the next, as long as the next weight is read at columns 32b + 8g + 4h + m.  So a wave carries its 32
-// rows through fp1's two layers, conv1 + bn1 and conv2 in registers; the last product's C/D layout leaves lane (j, h) with
-// the scores of channels 32b + 8g + 4h + m of row j, which it ranks itself before one exchange with lane j of the other half.
-typedef RowsArgsT<float> RowsArgs;
-
-// one 128 -> 128 layer on the registers: out = relu(W in + bias), both in the C/D layout (block b, register 4g + m of lane
-// (j, h) = channel 32b + 8g + 4h + m of row j)
-__device__ __forceinline__ void rows_layer(const float *__restrict__ W, long long ldw, const float *__restrict__ bias,
-                                           const f32x16 (&in)[ROWS_NB], f32x16 (&out)[ROWS_NB], int li, int lh)
-{
-#pragma unroll
-    for (int b2 = 0; b2 < ROWS_NB; ++b2) {
-        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const float *wr = W + (long long)(32 * b2 + li) * ldw + 4 * lh;
-#pragma unroll
-        for (int b = 0; b < ROWS_NB; ++b) {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 a = ld4(wr + 32 * b + 8 * gq);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, in[b][4 * gq + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, in[b][4 * gq + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, in[b][4 * gq + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, in[b][4 * gq + 3], acc, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const float4 bb = ld4(bias + 32 * b2 + 8 * gq + 4 * lh);
-            acc[4 * gq + 0] = relu_nan(acc[4 * gq + 0] + bb.x);
-            acc[4 * gq + 1] = relu_nan(acc[4 * gq + 1] + bb.y);
-            acc[4 * gq + 2] = relu_nan(acc[4 * gq + 2] + bb.z);
-            acc[4 * gq + 3] = relu_nan(acc[4 * gq + 3] + bb.w);
-        }
-        out[b2] = acc;
-    }
-}
-
-// X [P, 8 KQ] raw rows -> z = W4 relu(W3 relu(W2 relu(W1 x + b1) + b2) + b3) + b4, widths (128, 128, 128, CL <= 64);
-// scores[p][0:CL] = z and / or labels[p] = the first maximum of z among the allowed channels (-1: none allowed)
-template <int KQ>
-__global__ __launch_bounds__(256) void mlp_chain_rows_kernel(const RowsArgs g)
-{
-    __shared__ int s_cat[ROWS_MAX_CL];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int li = lane & 31, lh = lane >> 5;
-    const int CL = g.CL;
-    rows_load_cats(g, s_cat);
-    const long long row0 = (long long)blockIdx.x * CHAIN_ROWS + 32 * wave;
-    if (row0 >= g.P) return;                      // wave-uniform
-    const long long row = row0 + li;
-    const bool live = row < g.P;                  // a row past the end computes on a copy of the last row and stores nothing
-    const long long rowc = live ? row : g.P - 1;
-
-    f32x16 ha[ROWS_NB], hb[ROWS_NB];
+// The fp32 matrix pipe of the chains (infer_chain.h): v_mfma_f32_32x32x2_f32, two k per instruction, so a k-step of 8 columns
+// is four of them on the float4 a lane half loads.  Register 4g + m of lane half h of a finished block is channel
+// 8g + 4h + m -- the column the lane reads anyway: the "accumulator order" and the plain column order coincide, and a
+// weight is read as the fold wrote it (rows padded to 4 floats, NOT to a whole k-step: C1 = 196 ends in half a step).
+struct PipeF32 {
+    typedef float W;
+    typedef float4 Frag;
+    static constexpr int KSTEP = 8;
+    static constexpr bool PADDED = false;
+    static __device__ __forceinline__ Frag zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ Frag load_w(const W *p, int t) { return ld4(p + 8 * t); }
+    template <bool RELU, int K>      // K % 8 == 0: no fragment reaches past the row's end
+    static __device__ __forceinline__ Frag from_mem(const float *xr, int t, int)
     {
-        // B operand of layer 1: lane (j, h) holds X[row0 + j][8q + 4h + 0..3]
-        float4 xf[KQ];
-        const float *xr = g.X + rowc * g.ldx + 4 * lh;
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) xf[q] = ld4(xr + 8 * q);
-#pragma unroll
-        for (int b = 0; b < ROWS_NB; ++b) {
-            f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const float *wr = g.W[0] + (long long)(32 * b + li) * g.ldw[0] + 4 * lh;
-#pragma unroll
-            for (int q = 0; q < KQ; ++q) {
-                const float4 a = ld4(wr + 8 * q);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, xf[q].x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, xf[q].y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, xf[q].z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, xf[q].w, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const float4 bb = ld4(g.b[0] + 32 * b + 8 * gq + 4 * lh);
-                acc[4 * gq + 0] = relu_nan(acc[4 * gq + 0] + bb.x);
-                acc[4 * gq + 1] = relu_nan(acc[4 * gq + 1] + bb.y);
-                acc[4 * gq + 2] = relu_nan(acc[4 * gq + 2] + bb.z);
-                acc[4 * gq + 3] = relu_nan(acc[4 * gq + 3] + bb.w);
-            }
-            ha[b] = acc;
-        }
+        static_assert(K % 8 == 0, "whole k-steps");
+        const float4 v = ld4(xr + 8 * t);
+        return RELU ? relu4(v) : v;
     }
-    rows_layer(g.W[1], g.ldw[1], g.b[1], ha, hb, li, lh);
-    rows_layer(g.W[2], g.ldw[2], g.b[2], hb, ha, li, lh);
-
-    // layer 4, no ReLU: channels >= CL are zero A rows (the row index clamped for the load, the value zeroed)
-    RowsRank rk = rows_rank_begin(g, rowc);
-#pragma unroll
-    for (int b2 = 0; b2 < ROWS_MAX_CL / 32; ++b2) {
-        if (32 * b2 >= CL) break;                 // grid-uniform
-        f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const int c = 32 * b2 + li;
-        const bool ok = c < CL;
-        const float *wr = g.W[3] + (long long)(ok ? c : 0) * g.ldw[3] + 4 * lh;
-#pragma unroll
-        for (int b = 0; b < ROWS_NB; ++b) {
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                float4 a = ld4(wr + 32 * b + 8 * gq);
-                if (!ok) a = make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, ha[b][4 * gq + 0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, ha[b][4 * gq + 1], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, ha[b][4 * gq + 2], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, ha[b][4 * gq + 3], acc, 0, 0, 0);
-            }
-        }
-        rows_emit(g, acc, b2, lh, row, live, s_cat, rk);
+    static __device__ __forceinline__ Frag from_acc(const f32x16 &acc, int s)
+    {
+        return make_float4(acc[4 * s + 0], acc[4 * s + 1], acc[4 * s + 2], acc[4 * s + 3]);
     }
-    rows_finish(g, rk, lh, row, live);
-}
-
-template <int KQ>
-void rows_launch(const RowsArgs &g, hipStream_t st)
-{
-    const unsigned grid = (unsigned)((g.P + CHAIN_ROWS - 1) / CHAIN_ROWS);
-    hipLaunchKernelGGL((mlp_chain_rows_kernel<KQ>), dim3(grid), dim3(256), 0, st, g);
-}
-
-template <int KQ>
-void rows_dispatch(int kq, const RowsArgs &g, hipStream_t st)
-{
-    if (kq == KQ) rows_launch<KQ>(g, st);
-    else if constexpr (KQ > 1) rows_dispatch<KQ - 1>(kq, g, st);
-}
+    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 acc)
+    {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+    }
+    static __device__ __forceinline__ void block_end() {}      // the blocks of a layer stay in accumulators: nothing to fence
+    static bool pitch_ok(long long ld, int kin) { return ld >= kin && !(ld & 3); }
+};
 
 }  // namespace
 
@@ -327,73 +125,28 @@ int prifit_fold_bn(int njobs, const float *const *W, const int32_t *cout, const 
     return prifit_check_launch();
 }
 
-int prifit_mlp_chain_pool_supported(int C0, int C1, int C2, int pool_K)
-{
-    return (chain_shape(C0, C1, C2) >= 0 && (pool_K == 32 || pool_K == 64 || pool_K == 128)) ? 1 : 0;
-}
+int prifit_mlp_chain_pool_supported(int C0, int C1, int C2, int pool_K) { return chain_pool_supported(C0, C1, C2, pool_K); }
 
-long long prifit_mlp_chain_pool_workspace(int G, int pool_K, int C0, int C1, int C2)
-{
-    (void)G; (void)pool_K; (void)C0; (void)C1; (void)C2;
-    return 0;   // the intermediates live in registers
-}
+long long prifit_mlp_chain_pool_workspace(int, int, int, int, int) { return 0; }     // the intermediates live in registers
 
 int prifit_mlp_chain_pool_f32(const float *X, long long ldx, int G, int pool_K, int C0, int C1, int C2, const float *W1,
                               long long ldw1, const float *b1, const float *W2, long long ldw2, const float *b2, float *out,
-                              long long ldo, float *workspace, void *stream)
+                              long long ldo, float *, void *stream)
 {
-    (void)workspace;
-    if (!prifit_mlp_chain_pool_supported(C0, C1, C2, pool_K) || !X || !W1 || !b1 || !W2 || !b2 || !out || G <= 0 || ldx < C0 ||
-        (ldx & 3) || ldw1 < C0 || (ldw1 & 3) || ldw2 < C1 || (ldw2 & 3) || ldo < C2 || mis16(X) || mis16(W1) || mis16(b1) || mis16(W2) ||
-        mis16(b2) || (long long)G * pool_K > 0x7fffffffLL)
-        return PRIFIT_EINVAL;
-    ChainArgs g = {};
-    g.X = X; g.ldx = ldx; g.P = (long long)G * pool_K; g.G = G; g.pool_K = pool_K;
-    g.W1 = W1; g.b1 = b1; g.W2 = W2; g.b2 = b2; g.ldw1 = ldw1; g.ldw2 = ldw2; g.out = out; g.ldo = ldo;
-    hipStream_t st = as_stream(stream);
-    switch (chain_shape(C0, C1, C2)) {
-    case 0: chain_launch<32, 32, 64>(g, st); break;
-    case 1: chain_launch<64, 64, 128>(g, st); break;
-    case 2: chain_launch<64, 96, 128>(g, st); break;
-    case 3: chain_launch<128, 128, 256>(g, st); break;
-    default: chain_launch<128, 196, 256>(g, st); break;
-    }
-    return prifit_check_launch();
+    return chain_pool_run<PipeF32>(X, ldx, G, pool_K, C0, C1, C2, W1, ldw1, b1, W2, ldw2, b2, out, ldo, stream);
 }
 
-int prifit_mlp_chain_rows_supported(int K0, int L, const int32_t *widths)
-{
-    if (L != ROWS_L || !widths || K0 < 8 || K0 > ROWS_MAX_K0 || (K0 & 7)) return 0;
-    for (int l = 0; l + 1 < ROWS_L; ++l)
-        if (widths[l] != ROWS_W) return 0;
-    return (widths[ROWS_L - 1] >= 1 && widths[ROWS_L - 1] <= ROWS_MAX_CL) ? 1 : 0;
-}
+int prifit_mlp_chain_rows_supported(int K0, int L, const int32_t *widths) { return chain_rows_supported(K0, L, widths); }
 
-long long prifit_mlp_chain_rows_workspace(long long P, int K0, int L, const int32_t *widths)
-{
-    (void)P; (void)K0; (void)L; (void)widths;
-    return 0;   // the intermediates live in registers
-}
+long long prifit_mlp_chain_rows_workspace(long long, int, int, const int32_t *) { return 0; }     // likewise
 
 int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
                               const float *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
-                              int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
-                              float *workspace, void *stream)
+                              int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape, float *,
+                              void *stream)
 {
-    (void)workspace;
-    if (rows_check(K0, L, widths, X, ldx, P, W, ldw, b, scores, lds, labels, cat_of_label, shape_cat, rows_per_shape))
-        return PRIFIT_EINVAL;
-    const int CL = widths[ROWS_L - 1];
-    RowsArgs g = {};
-    for (int l = 0; l < ROWS_L; ++l) {
-        const int kin = l ? ROWS_W : K0;
-        if (!W[l] || !b[l] || ldw[l] < kin || (ldw[l] & 3) || mis16(W[l]) || mis16(b[l])) return PRIFIT_EINVAL;
-        g.W[l] = W[l]; g.b[l] = b[l]; g.ldw[l] = ldw[l];
-    }
-    g.X = X; g.ldx = ldx; g.P = P; g.CL = CL; g.scores = scores; g.lds = lds; g.labels = labels;
-    g.cat_of_label = labels ? cat_of_label : nullptr; g.shape_cat = labels ? shape_cat : nullptr; g.N = rows_per_shape;
-    rows_dispatch<ROWS_MAX_K0 / 8>(K0 / 8, g, as_stream(stream));
-    return prifit_check_launch();
+    return chain_rows_run<PipeF32>(X, ldx, P, K0, L, widths, W, ldw, b, scores, lds, labels, cat_of_label, shape_cat, rows_per_shape,
+                                   stream);
 }
 
 }  // extern "C"

@@ -21,11 +21,11 @@ The forward then runs on that buffer alone, under no_grad:
 No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
 to the live model: a shape the kernels do not take is an error.
 
-precision="bf16"  changes the arithmetic of the two on-chip chains only: prifit_mlp_chain_pool_bf16 and
-prifit_mlp_chain_rows_bf16 round every layer input to bf16 and accumulate in fp32 (v_mfma_f32_32x32x16_bf16).  Their weights
-are a second flat buffer of 16-bit patterns, written by ONE more launch of refresh() (prifit_pack_bf16_multi) in the column
-order the MFMA reads; the biases stay fp32 in `flat`.  Everything else -- sampling, grouping + first conv, the by-linearity
-products, SA3, fp3 / fp2, 3-NN, the separate-launch tail of forward() -- is the fp32 module's, launch for launch."""
+The two on-chip chains have one driver each (_chain_pool, _chain_rows) over a table keyed by precision (_CHAINS): entry
+point, queries, profiler tag and where a layer's weight lives.  precision="bf16"  changes their arithmetic
+only: prifit_mlp_chain_pool_bf16 and prifit_mlp_chain_rows_bf16 round every layer input to bf16 and accumulate in fp32.  Their
+weights are a second flat buffer of 16-bit patterns, written by ONE more launch of refresh() (prifit_pack_bf16_multi) in the
+column order the MFMA reads; the biases stay fp32 in `flat`.  Everything else is the fp32 module's, launch for launch."""
 import ctypes
 
 import numpy as np
@@ -42,6 +42,17 @@ _LL = ctypes.c_longlong
 _ALIGN = 64      # floats: every region of the flat buffer starts on a 256-byte boundary
 _ALIGN16 = 128   # 16-bit words: likewise in the bf16 buffer
 PRECISIONS = ("fp32", "bf16")
+
+# precision -> the pool chain's and the row chain's (entry point, _supported and _workspace query = stem + ..., profiler tag); a
+# chained layer's (weight, pitch) from its folded entry `ly` and its bf16 copy `w`; whether an untaken scale goes to _stack
+_CHAINS = {
+    "fp32": {"pool": ("prifit_mlp_chain_pool_f32", "prifit_mlp_chain_pool", "mlp_chain_pool"),
+             "rows": ("prifit_mlp_chain_rows_f32", "prifit_mlp_chain_rows", "mlp_chain_rows"),
+             "weight": lambda ly, w: (ly.W, ly.ldw), "pool_fallback": True},
+    "bf16": {"pool": ("prifit_mlp_chain_pool_bf16", "prifit_mlp_chain_pool_bf16", "mlp_chain_pool_bf16"),
+             "rows": ("prifit_mlp_chain_rows_bf16", "prifit_mlp_chain_rows_bf16", "mlp_chain_rows_bf16"),
+             "weight": lambda ly, w: (w.W, w.ldk), "pool_fallback": False},
+}
 
 
 class _Folded:
@@ -61,6 +72,7 @@ class _Packed:
 
     def __init__(self, layer, cols):
         self.layer, self.cols = layer, tuple(cols)
+        self.ldw = len(self.cols)
         self.off = -1
         self.W = None
 
@@ -330,9 +342,8 @@ class FrozenPartSeg(nn.Module):
         """(K0, widths) of the per-point tail; NotImplementedError where the row chain of this precision does not take it."""
         K0, widths = self._tail_kp, [ly.cout for ly in self._tail]
         L = len(widths)
-        entry, asks = (("prifit_mlp_chain_rows_bf16", "prifit_mlp_chain_rows_bf16_supported") if self._bf16 else
-                       ("prifit_mlp_chain_rows_f32", "prifit_mlp_chain_rows_supported"))
-        if not getattr(dll(), asks)(K0, L, (ctypes.c_int32 * L)(*widths)):
+        entry, stem, _ = _CHAINS[self.precision]["rows"]
+        if not getattr(dll(), stem + "_supported")(K0, L, (ctypes.c_int32 * L)(*widths)):
             raise NotImplementedError("FrozenPartSeg.labels(): a tail of %d input columns and widths %s is outside "
                                       "%s (4 layers, 128 / 128 / 128 / at most 64 parts, at most 160 "
                                       "columns); there is no fall-back" % (K0, tuple(widths), entry))
@@ -345,7 +356,7 @@ class FrozenPartSeg(nn.Module):
         its category, testing.py:141-144 -- an evaluation loop passes SegmentationEvaluator.cat_of_label and
         cat_of_label[target[:, 0]]; a cloud whose category has no part gets -1.  Both None: the arg-max over all parts.
         The first maximum wins, a NaN beats every number (prifit_seg_metrics' rules, bit for bit).
-        forward()'s route up to fp1's rows, then ONE launch (prifit_mlp_chain_rows_f32) over fp1's two layers, conv1 + bn1
+        forward()'s route up to fp1's rows, then ONE launch (_chain_rows) over fp1's two layers, conv1 + bn1
         and conv2: no [B N, 128] tensor, no log_softmax.  No fall-back: NotImplementedError for a tail the kernel refuses."""
         if (shape_cat is None) != (cat_of_label is None):
             raise ValueError("FrozenPartSeg.labels(): shape_cat and cat_of_label go together (both or neither)")
@@ -367,22 +378,9 @@ class FrozenPartSeg(nn.Module):
                 shape_cat = shape_cat.reshape(B).to(device=dev, dtype=torch.int32).contiguous()
                 cat_of_label = cat_of_label.reshape(parts).to(device=dev, dtype=torch.int32).contiguous()
             rows = self._fp_rows("fp1", l0_xyz, l1_xyz, skip, l1_up, K0)
-            P, L = B * N, len(widths)
             out = torch.empty(B, N, dtype=torch.int32, device=dev)
             scores = torch.empty(B, N, parts, dtype=torch.float32, device=dev) if return_scores else None
-            if self._bf16:
-                entry, Ws = "prifit_mlp_chain_rows_bf16", [w.W for w in self._tail_bf16]
-                nws = dll().prifit_mlp_chain_rows_bf16_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
-            else:
-                entry, Ws = "prifit_mlp_chain_rows_f32", [self._tail_w0.W] + [ly.W for ly in self._tail[1:]]
-                nws = dll().prifit_mlp_chain_rows_workspace(P, K0, L, (ctypes.c_int32 * L)(*widths))
-            ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-            flops = 2.0 * P * sum(k * c for k, c in zip([K0] + widths[:-1], widths))
-            with profiler.span(profiler.tag("mlp_chain_rows_bf16" if self._bf16 else "mlp_chain_rows", P, K0, *widths), flops):
-                call(entry, ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths),
-                     nn_ops._ptr_array(Ws), (ctypes.c_longlong * L)(*[W.stride(0) for W in Ws]),
-                     nn_ops._ptr_array([ly.b for ly in self._tail]), ptr(scores), _LL(parts), ptr(out), ptr(cat_of_label),
-                     ptr(shape_cat), N, ptr(ws), cur_stream())
+            self._chain_rows(rows, K0, widths, scores, out, cat_of_label, shape_cat, N)
         return (out, scores) if return_scores else out
 
     def _rows(self, parts, B, n, kp):
@@ -468,28 +466,43 @@ class FrozenPartSeg(nn.Module):
         for si, ((st, _), K, Y, C2) in enumerate(zip(scales, nsamples, Ys, outw)):
             win = wide[:, c0:c0 + C2]
             c0 += C2
-            C0, C1 = st[0].cout, st[1].cout
-            if self._bf16:
-                if not query("prifit_mlp_chain_pool_bf16_supported", C0, C1, C2, K):
-                    raise NotImplementedError("FrozenPartSeg(precision='bf16'): a scale of widths (%d, %d, %d) over %d samples is "
-                                              "outside prifit_mlp_chain_pool_bf16; there is no fall-back" % (C0, C1, C2, K))
-                G = B * S
-                w1, w2 = lv["bf16"][si]
-                nws = query("prifit_mlp_chain_pool_bf16_workspace", G, K, C0, C1, C2)
-                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-                with profiler.span(profiler.tag("mlp_chain_pool_bf16", G * K, C0, C1, C2), 2.0 * G * K * (C0 * C1 + C1 * C2)):
-                    call("prifit_mlp_chain_pool_bf16", ptr(Y), _LL(C0), G, K, C0, C1, C2, ptr(w1.W), _LL(w1.ldk), ptr(st[1].b),
-                         ptr(w2.W), _LL(w2.ldk), ptr(st[2].b), ptr(win), _LL(wide.stride(0)), ptr(ws), cur_stream())
-            elif query("prifit_mlp_chain_pool_supported", C0, C1, C2, K):
-                G = B * S
-                nws = query("prifit_mlp_chain_pool_workspace", G, K, C0, C1, C2)
-                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-                with profiler.span(profiler.tag("mlp_chain_pool", G * K, C0, C1, C2), 2.0 * G * K * (C0 * C1 + C1 * C2)):
-                    call("prifit_mlp_chain_pool_f32", ptr(Y), _LL(C0), G, K, C0, C1, C2, ptr(st[1].W), _LL(st[1].ldw), ptr(st[1].b),
-                         ptr(st[2].W), _LL(st[2].ldw), ptr(st[2].b), ptr(win), _LL(wide.stride(0)), ptr(ws), cur_stream())
-            else:
+            if not self._chain_pool(st, lv["bf16"][si] if self._bf16 else (None, None), Y, B * S, K, win, wide.stride(0)):
                 self._stack(Y, True, st, None, K, win)
         return new_xyz, wide.reshape(B, S, -1)
+
+    def _chain_pool(self, st, bf16, Y, G, K, win, ldo):
+        """Layers 2 + 3 + pool of scale `st` on its first-layer rows Y [G K, C0] in one launch -> win [G, C2] of pitch ldo; False
+        (fp32) or NotImplementedError (bf16) where the chain does not take the scale."""
+        chain = _CHAINS[self.precision]
+        entry, stem, tag = chain["pool"]
+        C0, C1, C2 = (ly.cout for ly in st)
+        if not query(stem + "_supported", C0, C1, C2, K):
+            if chain["pool_fallback"]:
+                return False
+            raise NotImplementedError("FrozenPartSeg(precision=%r): a scale of widths (%d, %d, %d) over %d samples is "
+                                      "outside %s; there is no fall-back" % (self.precision, C0, C1, C2, K, entry))
+        (W1, ld1), (W2, ld2) = (chain["weight"](ly, w) for ly, w in zip(st[1:], bf16))
+        nws = query(stem + "_workspace", G, K, C0, C1, C2)
+        ws = torch.empty(nws, dtype=torch.float32, device=Y.device) if nws else None
+        with profiler.span(profiler.tag(tag, G * K, C0, C1, C2), 2.0 * G * K * (C0 * C1 + C1 * C2)):
+            call(entry, ptr(Y), _LL(C0), G, K, C0, C1, C2, ptr(W1), _LL(ld1), ptr(st[1].b), ptr(W2), _LL(ld2), ptr(st[2].b),
+                 ptr(win), _LL(ldo), ptr(ws), cur_stream())
+        return True
+
+    def _chain_rows(self, rows, K0, widths, scores, labels, cat_of_label, shape_cat, N):
+        """The per-point tail on fp1's rows [P, K0] in one launch: scores [.., parts] (None: not wanted) and labels."""
+        chain = _CHAINS[self.precision]
+        entry, stem, tag = chain["rows"]
+        P, L = rows.shape[0], len(widths)
+        bf16 = self._tail_bf16 if self._bf16 else [None] * L
+        Ws, lds = zip(*(chain["weight"](ly, w) for ly, w in zip([self._tail_w0] + self._tail[1:], bf16)))
+        nws = getattr(dll(), stem + "_workspace")(P, K0, L, (ctypes.c_int32 * L)(*widths))
+        ws = torch.empty(nws, dtype=torch.float32, device=rows.device) if nws else None
+        flops = 2.0 * P * sum(k * c for k, c in zip([K0] + widths[:-1], widths))
+        with profiler.span(profiler.tag(tag, P, K0, *widths), flops):
+            call(entry, ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths), nn_ops._ptr_array(list(Ws)),
+                 (ctypes.c_longlong * L)(*lds), nn_ops._ptr_array([ly.b for ly in self._tail]), ptr(scores), _LL(widths[-1]),
+                 ptr(labels), ptr(cat_of_label), ptr(shape_cat), N, ptr(ws), cur_stream())
 
     def _fp_level(self, name, xyz1, xyz2, points1, points2):
         """Feature propagation: xyz1 [B,N,3], xyz2 [B,S,3] (None: S == 1), points1 [B,N,D1], points2 [B,S,D2] -> [B,N,C]."""
