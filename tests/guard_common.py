@@ -174,6 +174,17 @@ class Bufs:
     def dout(self, shape):
         return self.fout(tuple(shape[:-1]) + (2 * shape[-1],)).view(torch.float64)
 
+    def lin(self, t, poison):
+        """int64 input; both halves of every guard word pair hold `poison` (see iin), so a kernel that narrows a stray entry
+        to 32 bits finds the in-range value `poison`"""
+        v = self._guarded(tuple(t.shape[:-1]) + (2 * t.shape[-1],), int(poison))
+        v.view(torch.int64).copy_(t.to(torch.int64))
+        return v.view(torch.int64)
+
+    def lout(self, shape):
+        """int64 output: an entry the kernel did not write reads SENTINEL in both halves, far outside any index range"""
+        return self.fout(tuple(shape[:-1]) + (2 * shape[-1],)).view(torch.int64)
+
     def intact(self):
         if self.device != "cpu":
             torch.cuda.synchronize()

@@ -132,3 +132,24 @@ def test_bufs_put_every_tensor_in_guards_of_the_asked_size_and_see_one_word():
         base.view(torch.int32)[at] = 0
         with pytest.raises(AssertionError, match="1 guard word"):
             g.intact()
+
+
+def test_bufs_int64_views_sit_in_guards_and_see_half_a_word():
+    g = Bufs(64, 128, device="cpu")
+    li, lo = g.lin(torch.tensor([[5, 1 << 40, -2]]), 7), g.lout((2, 3))
+    assert li.dtype == lo.dtype == torch.int64 and li.shape == (1, 3) and lo.shape == (2, 3)
+    assert li.tolist() == [[5, 1 << 40, -2]] and li.data_ptr() % ALIGN == 0 and lo.data_ptr() % ALIGN == 0
+    unwritten = (SENTINEL << 32) | SENTINEL
+    assert bool((lo == unwritten).all()) and unwritten > (1 << 31)      # an unwritten entry is no index
+    (ibase, iv, ipoison), (obase, ov, _) = g.items
+    assert ipoison == 7 and int((ibase.view(torch.int32) == 7).sum()) == ibase.numel() - 6
+    for base, v in ((ibase, iv), (obase, ov)):
+        s = v.storage_offset() - base.storage_offset()
+        assert s >= 64 and base.numel() - s - v.numel() >= 128
+    g.intact()
+    lo.fill_(3)
+    g.intact()
+    at = ov.storage_offset() - obase.storage_offset() + ov.numel()       # the low half of the int64 behind the last entry
+    obase.view(torch.int32)[at] = 3
+    with pytest.raises(AssertionError, match="1 guard word"):
+        g.intact()
