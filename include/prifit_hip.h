@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 803
+#define PRIFIT_ABI_VERSION 804
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1101,6 +1101,32 @@ int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0
                               const float *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
                               int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
                               float *workspace, void *stream);
+
+/* The training half of that tail, for pre-training the classifier layer on the frozen network (train_partseg_shapenet.py:56-99,
+ * FrozenPartSeg.probe_step): the same four layers over raw rows X [P, ldx] -- layers 1 .. 3 exactly as in
+ * prifit_mlp_chain_rows_f32, z = W_4 a_3 + b_4 with C_L = widths[3] <= 64 -- ending in the segmentation loss, the gradient of
+ * the LAST layer and the accuracy count instead of scores.  W, ldw, b: HOST arrays as there; W_4 / b_4 may be the live
+ * conv2.weight [C_L, 128] (pitch 128) and conv2.bias, which have no BatchNorm to fold.
+ *   loss [4] = (mean over the kept rows of logsumexp(y) - y[t] with y = log_softmax(z): the softmax applied twice, models/
+ *     pointnet2_part_seg_msg.py:129,143; the number of kept rows; the number of kept rows whose FIRST maximum of z over all C_L
+ *     channels equals the label, in prifit_mlp_chain_rows_f32's order: a NaN beats every number; 0).  target [P] int64 with
+ *     prifit_cross_entropy_fwd's rules: -100 drops a row from numerator and denominator, any other label outside [0, C_L) makes
+ *     the loss and that row's contribution to dW / db NaN; no kept row: the loss is NaN (0 / 0, as torch), dW and db are zeros.
+ *   dW [C_L, lddw >= 128], db [C_L]: d loss / d W_4 and d loss / d b_4, OVERWRITTEN; columns 128 .. lddw - 1 are not written.
+ *     dz = (softmax(y) - onehot) / kept, dW = dz^T a_3, db = the column sums of dz.
+ * No [P, 128] and no [P, C_L] tensor is written and there are no floating-point atomics: a fixed grid of at most 256 workgroups
+ * walks the 128-row tiles, a workgroup keeps its dW partial in registers (the tile's a_3 and dz staged in LDS, dW = dz^T a_3
+ * on v_mfma_f32_32x32x2_f32) and writes one partial (64 x 128 + 64 + 4 floats) into `workspace`; a second launch sums the
+ * partials in a fixed order.  The same bits on every run.
+ * prifit_probe_head_supported answers as prifit_mlp_chain_rows_supported.  prifit_probe_head_workspace: floats of `workspace`,
+ * min(ceil(P / 128), 256) partials -- it does not grow with P beyond 256 tiles; 0 for an unsupported shape.
+ * PRIFIT_EINVAL without a launch: whatever prifit_mlp_chain_rows_f32 rejects of (X, ldx, P, K0, L, widths, W, ldw, b); target,
+ * dW, db, loss or workspace NULL; lddw < 128; dW not 16-byte aligned. */
+int prifit_probe_head_supported(int K0, int L, const int32_t *widths);
+long long prifit_probe_head_workspace(long long P, int K0, int L, const int32_t *widths);
+int prifit_probe_head_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                          const float *const *W, const long long *ldw, const float *const *b, const long long *target,
+                          float *dW, long long lddw, float *db, float *loss, float *workspace, void *stream);
 
 /* ---- frozen inference with bf16 arithmetic (FrozenPartSeg(model, precision="bf16")) ---- */
 

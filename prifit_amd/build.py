@@ -42,6 +42,7 @@ SOURCES = {
     "seg_metrics.hip": [],
     "infer.hip": [],
     "infer_bf16.hip": [],
+    "probe_head.hip": [],
     "edge_conv.hip": [],
     "dgcnn.hip": ["-ffp-contract=off"],
     "comm.hip": [],        # host-only: the RCCL export (RCCL itself is resolved with dlopen at run time)

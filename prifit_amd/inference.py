@@ -5,6 +5,7 @@
     seg, (l1, l2, l3), feat, zero, zero = frozen(xyz, cls_label, fps_start=None)
     seg = frozen.predict(xyz, cls_label)             # [B, N, num_parts] log-probabilities
     part = frozen.labels(xyz, cls_label, shape_cat, cat_of_label)   # [B, N] int32 part labels, one launch for the tail
+    loss_kept_correct = frozen.probe_step(xyz, cls_label, target)   # --init_cls: loss + conv2's gradient in one launch pair (3.9.3)
     frozen.refresh()                                 # re-fold from the live model (after more training)
 
 With fixed statistics a BatchNorm is a per-channel affine: s = gamma / sqrt(var + eps), bn(W x + b) = (s W) x + ((b - mean) s + beta).
@@ -18,6 +19,8 @@ The forward then runs on that buffer alone, under no_grad:
   * SA3, the feature-propagation stacks and the head: one folded product per layer on prifit_gemm_f32 (bias, ReLU on load
     through a unit-scale a_affine), then the existing pool / affine launch;
   * labels() only: fp1, conv1 + bn1, conv2 and the category-restricted arg-max in one launch (prifit_mlp_chain_rows_f32).
+  * probe_step() only: the same chain ending in the segmentation loss, the gradient of the live conv2 and the accuracy count
+    (prifit_probe_head_f32) -- the training half of the tail, for pre-training the classifier layer on the frozen network.
 No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
 to the live model: a shape the kernels do not take is an error.
 
@@ -382,6 +385,58 @@ class FrozenPartSeg(nn.Module):
             scores = torch.empty(B, N, parts, dtype=torch.float32, device=dev) if return_scores else None
             self._chain_rows(rows, K0, widths, scores, out, cat_of_label, shape_cat, N)
         return (out, scores) if return_scores else out
+
+    def probe_step(self, xyz, cls_label, target, fps_start=None):
+        """One iteration of the classifier-layer pre-training (train_partseg_shapenet.py:56-99, `--init_cls`):
+        xyz [B, C, N], cls_label as forward(), target [B, N] (or [B N]) int64 part labels -> a device tensor
+        (loss, kept rows, correct rows) of the eval-mode network with the LIVE conv2 of the source model, and
+        `conv2.weight.grad` / `conv2.bias.grad` of the source model = the gradient of that loss (allocated on first use,
+        overwritten after); an optimizer over conv2's two parameters steps on them.  loss is get_loss on the log-probabilities
+        (the softmax applied twice); -100 drops a point, any other label outside [0, parts) makes loss and gradient NaN.
+        labels()'s route up to fp1's rows, then ONE launch pair (prifit_probe_head_f32): no [B N, 128] tensor, no scores, no
+        autograd, no host read-back.  The folded copy of conv2 in the flat buffer is NOT kept up to date: refresh() after the
+        last step.  fp32 only (NotImplementedError with precision="bf16", and for a tail the kernel refuses)."""
+        if self.precision != "fp32":
+            raise NotImplementedError("FrozenPartSeg.probe_step(): fp32 only, this module runs precision=%r" % self.precision)
+        if xyz.dim() != 3:
+            raise ValueError("FrozenPartSeg.probe_step(): xyz must be [B, C, N], got %s" % (tuple(xyz.shape),))
+        B, _, N = xyz.shape
+        if not torch.is_tensor(target) or target.dtype != torch.int64:
+            raise ValueError("FrozenPartSeg.probe_step(): target must be an int64 tensor, got %s"
+                             % (target.dtype if torch.is_tensor(target) else type(target).__name__))
+        if tuple(target.shape) not in ((B, N), (B * N,)):
+            raise ValueError("FrozenPartSeg.probe_step(): target must be [%d, %d], got %s" % (B, N, tuple(target.shape)))
+        K0, widths = self._tail_kp, [ly.cout for ly in self._tail]
+        L = len(widths)
+        cw = (ctypes.c_int32 * L)(*widths)
+        if not dll().prifit_probe_head_supported(K0, L, cw):
+            raise NotImplementedError("FrozenPartSeg.probe_step(): a tail of %d input columns and widths %s is outside "
+                                      "prifit_probe_head_f32; there is no fall-back" % (K0, tuple(widths)))
+        conv2 = self._source.conv2
+        w, b = conv2.weight, conv2.bias
+        if b is None or w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.flat.device:
+            raise RuntimeError("FrozenPartSeg.probe_step(): conv2 of the source model must have a bias and contiguous fp32 "
+                               "parameters on %s" % self.flat.device)
+        for p in (w, b):
+            gr = p.grad
+            if gr is None or gr.dtype != torch.float32 or gr.shape != p.shape or not gr.is_contiguous() or gr.data_ptr() % 16:
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
+        with torch.no_grad():
+            pts, l0_xyz, l1_xyz, skip, l1_up, _, _ = self._trunk(xyz, cls_label, fps_start)
+            dev = pts.device
+            rows = self._fp_rows("fp1", l0_xyz, l1_xyz, skip, l1_up, K0)
+            tgt = target.to(dev).reshape(B * N).contiguous()
+            P, kin = B * N, widths[-2]
+            Ws = [self._tail_w0.W] + [ly.W for ly in self._tail[1:-1]] + [w.detach()]
+            lds = [self._tail_w0.W.stride(0)] + [ly.ldw for ly in self._tail[1:-1]] + [kin]
+            bs = [ly.b for ly in self._tail[:-1]] + [b.detach()]
+            out = torch.empty(4, dtype=torch.float32, device=dev)
+            ws = torch.empty(dll().prifit_probe_head_workspace(P, K0, L, cw), dtype=torch.float32, device=dev)
+            flops = 2.0 * P * (sum(k * c for k, c in zip([K0] + widths[:-1], widths)) + kin * widths[-1])
+            with profiler.span(profiler.tag("probe_head", P, K0, *widths), flops):
+                call("prifit_probe_head_f32", ptr(rows), _LL(K0), _LL(P), K0, L, cw, nn_ops._ptr_array(Ws), (ctypes.c_longlong * L)(*lds),
+                     nn_ops._ptr_array(bs), ptr(tgt), ptr(w.grad), _LL(kin), ptr(b.grad), ptr(out), ptr(ws), cur_stream())
+        return out[:3]
 
     def _rows(self, parts, B, n, kp):
         """[B n, kp] rows = the parts side by side, zero padded (the zeros are the flat buffer's: no fill launch)."""

@@ -9,6 +9,7 @@ process per GPU.
     ss = tr.selfsup_step(chamfer_points, quantile=.05, ...)     # upstream :436-451
     ss = tr.selfsup_step(chamfer_points, rotation_z=True, ...)  # + the augmentation flags of pretrain_partseg_shapenet.py:321-351
     val = tr.selfsup_validate(val_batches, ...)                 # its per-epoch validation pass, :377-402
+    hist = tr.init_classifier(batches)        # `--init_cls`, upstream :56-99 / :302-305: fit conv2 alone on the frozen network
     tr.save(path) / tr.load(path)             # checkpoint dict of upstream :467-475
     tr.finish()                               # REQUIRED after the last step under torch.distributed: the deferred
                                               # has-gradient check of the final exchange (ddp.FlatGradBucket.flush)
@@ -137,6 +138,72 @@ def graph_backbone(net, xyz, cls_label, fps_start):
     return graphed
 
 
+def init_classifier(model, batches, epochs=500, lr=0.1, momentum=0.5, augment=True, log=None):
+    """`--init_cls` (args_parser.py:43): after a pre-trained checkpoint is loaded, fit only the last layer (conv2, 128 ->
+    num_part) by logistic regression -- train_init_class, train_partseg_shapenet.py:56-99: the network in eval mode for the
+    whole of it, SGD(conv2.parameters(), lr=0.1, momentum=0.5), 500 epochs, scale + shift augmentation per batch.
+    Here the network is FROZEN (inference.freeze: folded BatchNorm, no autograd) and an iteration is one frozen forward up
+    to fp1's rows, one launch pair for loss + conv2's gradient (FrozenPartSeg.probe_step) and one FlatSGD launch.
+    batches: a re-iterable (list, DataLoader) of (points [B,N,3(+3)] channels-last, label, target [B,N] int64) as the
+    reference's loader yields them; label = the category, integers [B] / [B,1] or one-hot floats [B,16] / [B,1,16] (None:
+    zeros, as supervised_step); an optional fourth element is the sampling's fps_start, as supervised_step takes it (default:
+    drawn per call).  log: optional callable (epoch, mean loss, mean accuracy).
+    -> {"loss": [...], "acc": [...]}: per epoch the mean over the batches of the loss and of correct / points (the
+    reference's init_cls_loss / init_cls_acc), read back ONCE per epoch.
+    Nothing but conv2 changes: no BatchNorm buffer, no other parameter, not the trainer's optimizer state (its moments for
+    conv2 stay as they are, as the reference's Adam's do); conv2's parameters stay in the storage the trainer's optimizer
+    steps.  Per-rank: nothing is exchanged (6,450 parameters; every rank fits its own shard's layer unless the caller
+    broadcasts).  Networks without a frozen form (SSG, DGCNN) raise inference.freeze's TypeError."""
+    from . import inference
+    from .optim import FlatSGD
+    frozen = model.refresh() if isinstance(model, inference.FrozenPartSeg) else inference.freeze(model)
+    conv2 = frozen._source.conv2
+    params = [conv2.weight, conv2.bias]
+    home = [p.data for p in params]                    # FlatSGD re-homes p.data into a buffer of its own: put back below
+    had_grad = [p.grad for p in params]
+    opt = FlatSGD(params, lr=lr, momentum=momentum)
+    hist = {"loss": [], "acc": []}
+    dev = conv2.weight.device
+    try:
+        for epoch in range(epochs):
+            stats, points_seen = [], []
+            for points, label, target, *more in batches:
+                fps_start = more[0] if more else None
+                points = points.to(dev, torch.float32)
+                B, N, _ = points.shape
+                if augment:
+                    points = random_scale_shift(points)
+                xyz = points.transpose(2, 1).contiguous()
+                if label is None:
+                    onehot = torch.zeros(B, 1, 16, device=dev)
+                else:
+                    label = torch.as_tensor(label).to(dev)
+                    if label.dtype.is_floating_point and label.numel() == B * 16:
+                        onehot = label.reshape(B, 1, 16).float()
+                    else:
+                        onehot = F.one_hot(label.reshape(B).long(), 16).reshape(B, 1, 16).float()
+                stats.append(frozen.probe_step(xyz, onehot, torch.as_tensor(target).to(dev).long(), fps_start=fps_start))
+                points_seen.append(B * N)
+                opt.step()
+            if not stats:
+                raise ValueError("init_classifier: no batches")
+            s = torch.stack(stats).cpu()               # the epoch's one read-back
+            loss = float(s[:, 0].mean())
+            acc = float((s[:, 2] / torch.tensor(points_seen, dtype=torch.float32)).mean())
+            hist["loss"].append(loss)
+            hist["acc"].append(acc)
+            if log is not None:
+                log(epoch, loss, acc)
+    finally:
+        with torch.no_grad():
+            for p, h, g in zip(params, home, had_grad):
+                h.copy_(p.data)
+                p.data = h
+                p.grad = g
+        frozen.refresh()
+    return hist
+
+
 class Trainer:
     def __init__(self, model, num_part=50, learning_rate=0.001, decay_rate=1e-4, lr_decay=0.5, step_size=20, lmbda=1.0,
                  fused_adam=True, strict_seen=False, optimizer="Adam"):
@@ -173,6 +240,7 @@ class Trainer:
         self.speculative = SpeculativeRunner(model) if next(model.parameters()).is_cuda else None
         self.epoch = 0
         self.train_acc = 0.0
+        self.frozen = None         # inference.FrozenPartSeg of the model, built by init_classifier
 
     # ------------------------------------------------------------------ schedule (upstream :325-334)
     def set_epoch(self, epoch):
@@ -310,6 +378,16 @@ class Trainer:
         self._apply(None)
         return ss_loss.detach()
 
+    # ------------------------------------------------------------------ classifier-layer pre-training (upstream :56-99, :302-305)
+    def init_classifier(self, batches, epochs=500, lr=0.1, momentum=0.5, augment=True, log=None):
+        """`--init_cls`: fit conv2 alone on the frozen form of `self.model` -- see the module's init_classifier.  Leaves the
+        trainer's optimizer state, every other parameter and every BatchNorm buffer as they are.  The frozen form is kept
+        as `self.frozen` (re-folded from the live model at every call and once more at the end)."""
+        from . import inference
+        if self.frozen is None or self.frozen._source is not self.model:
+            self.frozen = inference.freeze(self.model)
+        return init_classifier(self.frozen, batches, epochs, lr, momentum, augment, log)
+
     # ------------------------------------------------------------------ validation (pretrain_partseg_shapenet.py:377-402)
     def selfsup_validate(self, batches, npoint=2048, quantile=0.01, msc_iterations=20, max_num_clusters=25, subset=None,
                          **loss_kwargs):
@@ -376,3 +454,22 @@ class Trainer:
         self.epoch = ck["epoch"]
         self.bucket.broadcast_parameters(0)
         return ck
+
+
+def train_init_class(classifier, criterion, trainDataLoader, num_classes, num_part, num_epoch=500):
+    """train_partseg_shapenet.py:56-99 with the reference's signature (plus the epoch count it hard-codes): pre-train the
+    classifier layer `conv2` of `classifier` by logistic regression on the frozen network and return the classifier in train
+    mode.  `criterion` must be the part-segmentation get_loss (cross-entropy on the log-probabilities): the fused loss is that
+    one.  The reference unpacks three values from a model that returns five (:78) and cannot run as written; this runs what it
+    states.  Sits on Trainer.init_classifier; `classifier` may be a Trainer (its model is pre-trained) or a model."""
+    from .models import pointnet2_part_seg_msg as _msg
+    if criterion is not None and not isinstance(criterion, _msg.get_loss):
+        raise TypeError("train_init_class: the fused loss is models.pointnet2_part_seg_msg.get_loss, got %s" % type(criterion).__name__)
+    if num_classes != 16:
+        raise ValueError("train_init_class: the part-segmentation network takes a 16-way category one-hot, got num_classes=%d" % num_classes)
+    trainer = classifier if isinstance(classifier, Trainer) else None
+    model = trainer.model if trainer is not None else classifier
+    if model.conv2.weight.shape[0] != num_part:
+        raise ValueError("train_init_class: conv2 has %d outputs, num_part=%d" % (model.conv2.weight.shape[0], num_part))
+    init_classifier(model, trainDataLoader, epochs=num_epoch)
+    return model.train()
