@@ -10,7 +10,7 @@ sums for its own BatchNorm, so no normalised activation is ever written to HBM.
 import collections
 import ctypes
 import os
-import types
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -74,9 +74,10 @@ def slab_sum(part):
     return out
 
 
-def gemm_stats_slabs(M, N, K):
-    """Number of column-statistics slabs a forward (NT) product of this shape writes."""
-    if _stream_ok(NT, M, N, K):
+def gemm_stats_slabs(M, N, K, aligned=True):
+    """Number of column-statistics slabs a forward (NT) product of this shape writes (aligned=False: gemm() keeps an operand
+    that is not 16-byte aligned off the streaming kernel)."""
+    if aligned and _stream_ok(NT, M, N, K):
         return query("prifit_gemm_stream_slabs", M, K)
     t = query("prifit_gemm_stats_tile_m", M, N)
     return (M + t - 1) // t
@@ -144,16 +145,141 @@ def _weight_grad(dY, P, Cout, Ain, Kin, a_affine, out=None):
     return dW
 
 
-def _forward_kernel(last, pool_K, aligned, has_affine, P, Cout, Kin):
-    """The launch that forms a training-mode layer's product.  "stream_pool" / "tiled_pool": a max-pooled last layer whose epilogue
-    also emits (max, argmax, min, argmin) per 32 rows and column, so that the pool reads those candidates (1/8 of Y) instead
-    of Y -- on the streaming kernel, or on the tiled (persistent) one (SA2's 256-wide last layers).  "gemm": everything else."""
-    if last and pool_K and pool_K % 32 == 0 and _FUSE_POOL_FWD and aligned and has_affine:
+class _FwdRoute(NamedTuple):
+    """How one layer of SharedMLPFn.forward comes about (DESIGN.md 3.1 has the entry points in order): the arm (a key of
+    _FWD_ARMS), where the layer's column-statistics slab comes from ("front": the launch that computed layer 0; "launch": the
+    arm's own product; None: eval mode, running statistics) and whether the arm leaves pool candidates.
+      preact         layer 0 computed elsewhere (cfg["front"])
+      norows_gather  layer 1 over first-layer rows that were never stored: the streaming product gathers them from U
+      eval           the general product with bias, no statistics
+      stream_pool / tiled_pool   a max-pooled last layer whose epilogue also emits (max, argmax, min, argmin) per 32 rows and
+                     column, so that the pool reads those candidates (1/8 of Y) instead of Y -- on the streaming kernel, or on
+                     the tiled (persistent) one (SA2's 256-wide last layers)
+      gemm           the general product with a statistics slab: everything else"""
+    arm: str
+    slab: Optional[str]
+    cand: bool
+
+
+def _forward_route(l, L, P, Cout, Kin, pool_K, training, mode, aligned, has_affine):
+    """The route of layer l of an L-layer stack over P rows (Cout x Kin weights); launches nothing, allocates nothing, reads the
+    module switches and query(...) only, at every call (tests flip the switches between two calls).  mode: as in
+    _backward_route; aligned: the layer's input rows and weights are 16-byte aligned with a row stride % 4 == 0; has_affine:
+    the layer below hands its (scale, shift) on (every layer but the first of a "plain" stack)."""
+    if l == 0 and mode != "plain":
+        return _FwdRoute("preact", "front", False)
+    if l == 1 and mode == "norows":
+        assert training and L >= 3, "norows: a training-mode stack of >= 3 layers (pointnet_util._norows_scales)"
+        return _FwdRoute("norows_gather", "launch", False)
+    if not training:
+        return _FwdRoute("eval", None, False)
+    if l == L - 1 and pool_K and pool_K % 32 == 0 and _FUSE_POOL_FWD and aligned and has_affine:
         if _stream_ok(NT, P, Cout, Kin):
-            return "stream_pool"
+            return _FwdRoute("stream_pool", "launch", True)
         if query("prifit_gemm_pool_supported", P, Cout, Kin):
-            return "tiled_pool"
-    return "gemm"
+            return _FwdRoute("tiled_pool", "launch", True)
+    return _FwdRoute("gemm", "launch", False)
+
+
+class _FwdLayer(NamedTuple):
+    """What a forward arm reads: the stack's rows P and device, the layer's widths, its input rows `prev` (None: never stored,
+    the norows arm re-forms them from front.U / Vc) with the (scale, shift) `aff` of the layer below applied on load (None: raw
+    input), its contiguous weight W and bias, the stack's FrontEnd (or None), and `aligned` as _forward_route takes it."""
+    P: int
+    Cout: int
+    Kin: int
+    dev: torch.device
+    prev: Optional[torch.Tensor]
+    aff: Optional[tuple]
+    W: Optional[torch.Tensor]
+    bias: Optional[torch.Tensor]
+    front: Optional[tuple]
+    aligned: bool
+
+
+# The forward arms: f(ly) -> (Y [P, Cout], the slab of its column statistics or None, the pool candidates or None).
+
+def _fwd_preact(ly):
+    return ly.prev, ly.front.slab, None
+
+
+def _fwd_eval(ly):
+    Y = torch.empty(ly.P, ly.Cout, dtype=torch.float32, device=ly.dev)
+    gemm(NT, ly.P, ly.Cout, ly.Kin, ly.prev, ly.prev.stride(0), ly.W, ly.Kin, Y, ly.Cout, a_affine=ly.aff, bias=ly.bias)
+    return Y, None, None
+
+
+def _fwd_norows_gather(ly):
+    P, Cout, Kin, nr = ly.P, ly.Cout, ly.Kin, ly.front
+    assert ly.prev is None
+    Y = torch.empty(P, Cout, dtype=torch.float32, device=ly.dev)
+    slab = torch.empty(query("prifit_gemm_stream_slabs", P, Kin), 2, Cout, dtype=torch.float32, device=ly.dev)
+    with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, "gather"), 4.0 * (P * Cout + P + Cout * Kin)):
+        call("prifit_gemm_stream_gather_f32", P, Cout, ptr(nr.idx), ptr(nr.U), ptr(nr.Vc), nr.N, nr.S,
+             nr.K, ptr(ly.W), _LL(Kin), ptr(Y), _LL(Cout), ptr(ly.aff[0]), ptr(ly.aff[1]), ptr(ly.bias), ptr(slab),
+             cur_stream())
+    return Y, slab, None
+
+
+def _fwd_stream_pool(ly):
+    P, Cout, Kin, prev, dev = ly.P, ly.Cout, ly.Kin, ly.prev, ly.dev
+    Y = torch.empty(P, Cout, dtype=torch.float32, device=dev)
+    slab = torch.empty(query("prifit_gemm_stream_slabs", P, Kin), 2, Cout, dtype=torch.float32, device=dev)
+    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
+    with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, 1), 4.0 * (P * Kin + P * Cout + Cout * Kin)):
+        call("prifit_gemm_stream_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(ly.W), _LL(Kin),
+             ptr(Y), _LL(Cout), ptr(ly.aff[0]), ptr(ly.aff[1]), ptr(ly.bias), ptr(slab), ptr(cand), cur_stream())
+    return Y, slab, cand
+
+
+def _fwd_tiled_pool(ly):
+    P, Cout, Kin, prev, dev = ly.P, ly.Cout, ly.Kin, ly.prev, ly.dev
+    Y = torch.empty(P, Cout, dtype=torch.float32, device=dev)
+    slab = torch.empty(gemm_stats_slabs(P, Cout, Kin), 2, Cout, dtype=torch.float32, device=dev)   # (not a streaming shape)
+    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
+    with profiler.span(profiler.tag("gemm_nt_bn128", P, Cout, Kin, "pool"), 2.0 * P * Cout * Kin):
+        call("prifit_gemm_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(ly.W), _LL(Kin), ptr(Y),
+             _LL(Cout), ptr(ly.aff[0]), ptr(ly.aff[1]), ptr(ly.bias), ptr(slab), ptr(cand), cur_stream())
+    return Y, slab, cand
+
+
+def _fwd_gemm(ly):
+    P, Cout, Kin = ly.P, ly.Cout, ly.Kin
+    Y = torch.empty(P, Cout, dtype=torch.float32, device=ly.dev)
+    slab = torch.empty(gemm_stats_slabs(P, Cout, Kin, ly.aligned), 2, Cout, dtype=torch.float32, device=ly.dev)
+    gemm(NT, P, Cout, Kin, ly.prev, ly.prev.stride(0), ly.W, Kin, Y, Cout, a_affine=ly.aff, bias=ly.bias, stats=slab)
+    return Y, slab, None
+
+
+_FWD_ARMS = {"preact": _fwd_preact, "eval": _fwd_eval, "norows_gather": _fwd_norows_gather, "stream_pool": _fwd_stream_pool,
+             "tiled_pool": _fwd_tiled_pool, "gemm": _fwd_gemm}
+
+
+def _forward_output(cfg, Y, aff, cand, P, dev):
+    """The stack's output from its last layer's rows Y and coefficients -> (out, arg): the max over each group of
+    cfg["pool_K"] rows of relu(scale Y + shift) with its int32 winners (from `cand`, where the last layer's arm left pool
+    candidates, else from Y), or relu(scale Y + shift) itself and None."""
+    CL, pool_K = Y.shape[1], cfg["pool_K"]
+    if not pool_K:
+        out = torch.empty(P, CL, dtype=torch.float32, device=dev)
+        call("prifit_affine_relu", ptr(Y), _LL(CL), ptr(aff[0]), ptr(aff[1]), P, CL, 0, _F(0.0), ptr(out), _LL(CL), cur_stream())
+        return out, None
+    G = P // pool_K
+    # pool_out: a [G, CL] column window of the level's concatenated output (the scales of a multi-scale level write
+    # side by side: no torch.cat); the pool kernels take a leading dimension
+    out = cfg.get("pool_out")
+    if out is None:
+        out = torch.empty(G, CL, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (G, CL) or out.stride(1) != 1 or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError("pool_out must be a [G, C] fp32 column window on the input's device")
+    arg = torch.empty(G, CL, dtype=torch.int32, device=dev)
+    if cand is not None:
+        call("prifit_pool_from_candidates", ptr(cand), ptr(aff[0]), ptr(aff[1]), G, pool_K, CL, 0, _F(0.0),
+             ptr(out), _LL(out.stride(0)), ptr(arg), None, cur_stream())
+    else:
+        call("prifit_pool_fwd", ptr(Y), _LL(CL), ptr(aff[0]), ptr(aff[1]), G, pool_K, CL, 0, _F(0.0),
+             ptr(out), _LL(out.stride(0)), ptr(arg), cur_stream())
+    return out, arg
 
 
 # How one layer of SharedMLPFn.backward gets from (G, its coefficients) to the gradient of the layer below.
@@ -210,9 +336,39 @@ def _backward_route(l, L, P, Cout, Kin, pool_K, training, mode, need_dW, need_dx
     return _Route("plain", "stream" if _stream_ok(NN, P, Kin, Cout) else "tiled", True)
 
 
-# The routes: f(ly, route) -> (G_prev, dW or None, the slab of sums left for the layer below or None, extra).  ly: the layer's
-# sizes, tensors and coefficients as SharedMLPFn.backward collects them (Yp, aff_p, stats_p: the rows, (scale, shift) and
-# (mean, invstd) of the layer below; dW: the layer's zero-filled [Cout, Kin] window of the stack's arena, None if not wanted).
+class _BwdLayer(NamedTuple):
+    """What a route reads, built by SharedMLPFn.backward once per layer.  Every route: P, Cout, dev, G (the gradient w.r.t. the
+    layer's ReLU or pooled output), Y, the layer's (scale, shift) and its backward coefficients ca, cb, cd (dY = ca Gm + cb Y +
+    cd).  The routes with a layer below (pool, bn, norows, plain): Kin, W, Yp / aff_p / stats_p -- the rows, (scale, shift) and
+    (mean, invstd) of the layer below (x, None, None at layer 0) -- and dW, the layer's zero-filled [Cout, Kin] window of the
+    stack's arena (None if not wanted).  pool and plain: pooled, pool_K, arg (the pool's winners).  direct0, gather0, norows:
+    front (the stack's FrontEnd); gather0: bias0.  need_dW: direct0, plain; want_db (eval mode, the bias wants sum(dY)): plain."""
+    P: int
+    Cout: int
+    Kin: int
+    dev: torch.device
+    pooled: bool
+    pool_K: int
+    arg: Optional[torch.Tensor]
+    G: torch.Tensor
+    Y: Optional[torch.Tensor]
+    W: Optional[torch.Tensor]
+    scale: torch.Tensor
+    shift: torch.Tensor
+    ca: torch.Tensor
+    cb: torch.Tensor
+    cd: torch.Tensor
+    Yp: Optional[torch.Tensor]
+    aff_p: Optional[tuple]
+    stats_p: Optional[tuple]
+    front: Optional[tuple]
+    bias0: Optional[torch.Tensor]
+    dW: Optional[torch.Tensor]
+    need_dW: bool
+    want_db: bool
+
+
+# The routes: f(ly, route) -> (G_prev, dW or None, the slab of sums left for the layer below or None, extra).
 # extra: gather0's dVc; the plain route's dY.sum(0) where ly.want_db asks for it; None otherwise.
 
 def _fused_bwd(ly, route, Ttab=None):
@@ -426,6 +582,80 @@ def front_end_args(cfg, convs, bns, front):
     return cfg, ts
 
 
+class _SavedLayer(NamedTuple):
+    """What SharedMLPFn.forward keeps of one layer: its pre-activation rows Y [P, Cout] (layer 0 of a front end: x, None in mode
+    "norows"), its contiguous weight (None: layer 0 of a front end, which has no product) and the BatchNorm coefficients
+    applied to Y -- relu(scale Y + shift) is the layer's output, (mean, invstd) the statistics behind them."""
+    Y: Optional[torch.Tensor]
+    W: Optional[torch.Tensor]
+    scale: torch.Tensor
+    shift: torch.Tensor
+    mean: torch.Tensor
+    invstd: torch.Tensor
+
+
+class _SavedStack(NamedTuple):
+    """What SharedMLPFn.forward hands to backward: one _SavedLayer per layer, the input x, the pool's int32 winners (None:
+    not pooled), the rows P and device, how layer 0 came about (_backward_route's mode) with the front end's record (the
+    fused modes read it in backward), layer 0's bias slot (gather mode's csr backward re-forms y1 from it) and cfg without
+    "front" / "pool_out"."""
+    layers: list
+    x: Optional[torch.Tensor]
+    arg: Optional[torch.Tensor]
+    P: int
+    dev: torch.device
+    mode: str
+    front: Optional[tuple]
+    bias0: Optional[torch.Tensor]
+    cfg: dict
+
+
+def _layer_dims(W, Y, front):
+    """(Cout, Kin) of a layer from its weight; a front end's layer 0 (no weight): the width of its rows Y (of front.U where
+    they are not stored), 0."""
+    if W is not None:
+        return W.shape
+    return (front.U.shape[-1] if Y is None else Y.shape[1]), 0
+
+
+def _grad_arena(st, needs):
+    """One zero-filled arena for every weight gradient of the stack (split-K adds into it) and, in training, its (exactly
+    zero) bias gradients -> (arena or None, {layer: (weight offset, weight size, bias offset, bias size)})."""
+    wslots, total = {}, 0
+    for l, sv in enumerate(st.layers):
+        if sv.W is None:
+            continue
+        n = sv.W.numel() if needs[2 + 6 * l] else 0
+        nb = sv.W.shape[0] if (st.cfg["training"] and needs[2 + 6 * l + 1]) else 0
+        wslots[l] = (total, n, total + n, nb)
+        total += n + nb
+    return (zero_pool.zeros(total, device=st.dev) if total else None), wslots
+
+
+def _bwd_coefficients(st, sv, Cout, pooled, G, fused_red):
+    """The layer's backward coefficients [5, C] = dgamma, dbeta, a, b, d (dY = a Gm + b Y + d): prifit_bn_bwd_finalize from the
+    slab of (m1, m2) sums -- prifit_pool_bwd_reduce for a pooled layer, else `fused_red` where the route of the layer above
+    has left it, else prifit_bn_relu_bwd_reduce."""
+    P, pool_K, dev = st.P, st.cfg["pool_K"], st.dev
+    coefs = torch.empty(5, Cout, dtype=torch.float32, device=dev).unbind(0)
+    if pooled:
+        prs = query("prifit_pool_reduce_groups_per_slab")
+        slab = torch.empty((P // pool_K + prs - 1) // prs, 2, Cout, dtype=torch.float32, device=dev)
+        call("prifit_pool_bwd_reduce", ptr(G), _LL(G.stride(0)), ptr(sv.Y), _LL(Cout), ptr(st.arg), ptr(sv.scale),
+             ptr(sv.shift), ptr(sv.mean), ptr(sv.invstd), P // pool_K, pool_K, Cout, 0, _F(0.0), ptr(slab), cur_stream())
+    elif fused_red is not None:
+        slab = fused_red
+    else:
+        rps = _rows_per_slab()
+        slab = torch.empty((P + rps - 1) // rps, 2, Cout, dtype=torch.float32, device=dev)
+        call("prifit_bn_relu_bwd_reduce", ptr(G), _LL(G.stride(0)), ptr(sv.Y), _LL(Cout), ptr(sv.scale),
+             ptr(sv.shift), ptr(sv.mean), ptr(sv.invstd), P, Cout, 0, _F(0.0), ptr(slab), cur_stream())
+    dgamma, dbeta, ca, cb, cd = coefs
+    call("prifit_bn_bwd_finalize", ptr(slab), slab.shape[0], Cout, _D(float(P)), int(st.cfg["training"]), ptr(sv.scale),
+         ptr(sv.mean), ptr(sv.invstd), ptr(dgamma), ptr(dbeta), ptr(ca), ptr(cb), ptr(cd), cur_stream())
+    return coefs
+
+
 class SharedMLPFn(torch.autograd.Function):
     """(conv1x1 + BatchNorm + ReLU) x L [+ max over the K samples of each group].
 
@@ -447,56 +677,22 @@ class SharedMLPFn(torch.autograd.Function):
         mode = "plain" if front is None else front.mode
         # norows: layer 0's pre-activation rows are not stored (x is None); they are re-formed from (idx, U, Vc) by the
         # three kernels that consume them
-        nr = front if mode == "norows" else None
-        if nr is not None:
-            P, dev = nr.B * nr.S * nr.K, nr.U.device
+        if mode == "norows":
+            P, dev = front.B * front.S * front.K, front.U.device
         else:
-            P, K0 = x.shape
-            dev = x.device
+            P, dev = x.shape[0], x.device
         training = cfg["training"]
-        Ys, affines, stats_saved, Ws = [], [], [], []
-        prev, prev_aff = x, None
-        cand = None
+        layers, prev, aff, cand = [], x, None, None
         for l in range(L):
             W, b, gamma, beta, rmean, rvar = tensors[6 * l:6 * l + 6]
-            preact = l == 0 and front is not None
-            if preact:
-                W, Cout, Kin, Y = None, (nr.U.shape[-1] if nr is not None else x.shape[1]), 0, x
-            else:
-                W = W.contiguous()
-                Cout, Kin = W.shape
-                assert Kin == (nr.U.shape[-1] if (l == 1 and nr is not None) else prev.shape[1]), (Kin, l)
-                Y = torch.empty(P, Cout, dtype=torch.float32, device=dev)
+            W = None if (l == 0 and front is not None) else W.contiguous()   # (a front end's layer 0 has no product)
+            Cout, Kin = _layer_dims(W, x, front)
+            assert W is None or Kin == (front.U.shape[-1] if prev is None else prev.shape[1]), (Kin, l)
+            aligned = (W is not None and prev is not None and prev.stride(0) % 4 == 0 and prev.data_ptr() % 16 == 0 and
+                       W.data_ptr() % 16 == 0)
+            route = _forward_route(l, L, P, Cout, Kin, cfg["pool_K"], training, mode, aligned, aff is not None)
             # slab: the column statistics of Y, written by the launch that produces the layer (training)
-            if preact:
-                slab = front.slab
-            elif not training:
-                gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b)
-            elif l == 1 and nr is not None:
-                # layer 2 on rows that were never stored: the streaming product gathers them from U (prifit_gemm_stream_gather_f32)
-                slab = torch.empty(query("prifit_gemm_stream_slabs", P, Kin), 2, Cout, dtype=torch.float32, device=dev)
-                with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, "gather"), 4.0 * (P * Cout + P + Cout * Kin)):
-                    call("prifit_gemm_stream_gather_f32", P, Cout, ptr(nr.idx), ptr(nr.U), ptr(nr.Vc), nr.N, nr.S,
-                         nr.K, ptr(W), _LL(Kin), ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab),
-                         cur_stream())
-            else:
-                aligned = prev.stride(0) % 4 == 0 and prev.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
-                tile_m = query("prifit_gemm_stats_tile_m", P, Cout)
-                nslab = gemm_stats_slabs(P, Cout, Kin) if aligned else (P + tile_m - 1) // tile_m
-                slab = torch.empty(nslab, 2, Cout, dtype=torch.float32, device=dev)
-                kernel = _forward_kernel(l == L - 1, cfg["pool_K"], aligned, prev_aff is not None, P, Cout, Kin)
-                if kernel == "gemm":
-                    gemm(NT, P, Cout, Kin, prev, prev.stride(0), W, Kin, Y, Cout, a_affine=prev_aff, bias=b, stats=slab)
-                else:
-                    cand = torch.empty(P // 32, 4, Cout, dtype=torch.float32, device=dev)
-                    if kernel == "stream_pool":
-                        with profiler.span(profiler.tag("gemm_stream_nt", P, Cout, Kin, 1), 4.0 * (P * Kin + P * Cout + Cout * Kin)):
-                            call("prifit_gemm_stream_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin),
-                                 ptr(Y), _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
-                    else:
-                        with profiler.span(profiler.tag("gemm_nt_bn128", P, Cout, Kin, "pool"), 2.0 * P * Cout * Kin):
-                            call("prifit_gemm_pool_f32", P, Cout, Kin, ptr(prev), _LL(prev.stride(0)), ptr(W), _LL(Kin), ptr(Y),
-                                 _LL(Cout), ptr(prev_aff[0]), ptr(prev_aff[1]), ptr(b), ptr(slab), ptr(cand), cur_stream())
+            Y, slab, cand = _FWD_ARMS[route.arm](_FwdLayer(P, Cout, Kin, dev, prev, aff, W, b, front, aligned))
             if training:
                 # the layer's coefficients [4, C] = scale, shift, mean, invstd, written by prifit_bn_finalize from that slab
                 scale, shift, mean, invstd = torch.empty(4, Cout, dtype=torch.float32, device=dev).unbind(0)
@@ -505,102 +701,43 @@ class SharedMLPFn(torch.autograd.Function):
                      ptr(mean), ptr(invstd), cur_stream())
             else:
                 scale, shift, mean, invstd = _eval_coeffs(gamma, beta, rmean, rvar, cfg["eps"])
-            Ys.append(Y)
-            Ws.append(W)
-            affines.append((scale, shift))
-            stats_saved.append((mean, invstd))
-            prev, prev_aff = Y, (scale, shift)
-        CL = Ys[-1].shape[1]
-        pool_K = cfg["pool_K"]
-        arg = None
-        if pool_K:
-            G = P // pool_K
-            # pool_out: a [G, CL] column window of the level's concatenated output (the scales of a multi-scale level write
-            # side by side: no torch.cat); the pool kernels take a leading dimension
-            out = cfg.get("pool_out")
-            if out is None:
-                out = torch.empty(G, CL, dtype=torch.float32, device=dev)
-            elif tuple(out.shape) != (G, CL) or out.stride(1) != 1 or out.dtype != torch.float32 or out.device != dev:
-                raise ValueError("pool_out must be a [G, C] fp32 column window on the input's device")
-            arg = torch.empty(G, CL, dtype=torch.int32, device=dev)
-            if cand is not None:
-                call("prifit_pool_from_candidates", ptr(cand), ptr(prev_aff[0]), ptr(prev_aff[1]), G, pool_K, CL, 0, _F(0.0),
-                     ptr(out), _LL(out.stride(0)), ptr(arg), None, cur_stream())
-            else:
-                call("prifit_pool_fwd", ptr(Ys[-1]), _LL(CL), ptr(prev_aff[0]), ptr(prev_aff[1]), G, pool_K, CL, 0, _F(0.0),
-                     ptr(out), _LL(out.stride(0)), ptr(arg), cur_stream())
-        else:
-            out = torch.empty(P, CL, dtype=torch.float32, device=dev)
-            call("prifit_affine_relu", ptr(Ys[-1]), _LL(CL), ptr(prev_aff[0]), ptr(prev_aff[1]), P, CL, 0, _F(0.0),
-                 ptr(out), _LL(CL), cur_stream())
-        ctx.cfg = {k: v for k, v in cfg.items() if k not in ("front", "pool_out")}
-        # how layer 0 came about (_backward_route's mode) and the front end's record (the fused modes read it in backward)
-        ctx.mode, ctx.front = mode, front
-        ctx.L = L
-        ctx.P, ctx.dev = P, dev
-        assert nr is None or (training and L >= 3 and Ys[0] is None)
-        ctx.saved = (x, Ys, Ws, affines, stats_saved, arg)
-        ctx.bias0 = tensors[1]
+            layers.append(_SavedLayer(Y, W, scale, shift, mean, invstd))
+            prev, aff = Y, (scale, shift)
+        out, arg = _forward_output(cfg, prev, aff, cand, P, dev)
+        # (an attribute, not save_for_backward: nothing saved here is an output of this function, so no reference cycle)
+        ctx.stack = _SavedStack(layers, x, arg, P, dev, mode, front, tensors[1],
+                                {k: v for k, v in cfg.items() if k not in ("front", "pool_out")})
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        cfg, L, needs = ctx.cfg, ctx.L, ctx.needs_input_grad
-        x, Ys, Ws, affines, stats_saved, arg = ctx.saved
-        training, pool_K = cfg["training"], cfg["pool_K"]
-        P, dev, front, mode = ctx.P, ctx.dev, ctx.front, ctx.mode
+        st, needs = ctx.stack, ctx.needs_input_grad
+        L, P, dev, front = len(st.layers), st.P, st.dev, st.front
+        training, pool_K = st.cfg["training"], st.cfg["pool_K"]
         # a pooled stack takes its gradient with any row stride (a column slice of the concatenated multi-scale gradient:
         # every kernel that reads it has a leading dimension) -- no copy; the unpooled paths index rows densely
         if not (pool_K and L > 1 and gout.dim() == 2 and gout.stride(1) == 1 and gout.stride(0) % 4 == 0 and
                 gout.data_ptr() % 16 == 0):
             gout = gout.contiguous()
-        rps = _rows_per_slab()
         grads = [None] * (6 * L)
-        # one zero-filled arena for every weight gradient (split-K adds into it) and, in training, the (exactly
-        # zero) bias gradients of this stack
-        wslots, total = {}, 0
-        for l in range(L):
-            if Ws[l] is None:
-                continue
-            n = Ws[l].numel() if needs[2 + 6 * l] else 0
-            nb = Ws[l].shape[0] if (training and needs[2 + 6 * l + 1]) else 0
-            wslots[l] = (total, n, total + n, nb)
-            total += n + nb
-        arena = zero_pool.zeros(total, device=dev) if total else None
+        arena, wslots = _grad_arena(st, needs)
         G_in = gout  # gradient w.r.t. the ReLU output of layer l (or pooled output for the last layer)
         fused_red = None   # the slab of (m1, m2) sums of layer l, where the route of the layer above has left it
         for l in range(L - 1, -1, -1):
-            Y, W = Ys[l], Ws[l]
-            Cout, Kin = W.shape if W is not None else ((front.U.shape[-1] if Y is None else Y.shape[1]), 0)
-            scale, shift = affines[l]
-            mean, invstd = stats_saved[l]
+            sv, below = st.layers[l], st.layers[l - 1] if l > 0 else None
+            Cout, Kin = _layer_dims(sv.W, sv.Y, front)
             pooled = l == L - 1 and bool(pool_K)
-            # the layer's backward coefficients [5, C] = dgamma, dbeta, a, b, d (dY = a Gm + b Y + d): prifit_bn_bwd_finalize
-            # from the slab of (m1, m2) sums
-            dgamma, dbeta, ca, cb, cd = torch.empty(5, Cout, dtype=torch.float32, device=dev).unbind(0)
-            if pooled:
-                prs = query("prifit_pool_reduce_groups_per_slab")
-                slab = torch.empty((P // pool_K + prs - 1) // prs, 2, Cout, dtype=torch.float32, device=dev)
-                call("prifit_pool_bwd_reduce", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(arg), ptr(scale),
-                     ptr(shift), ptr(mean), ptr(invstd), P // pool_K, pool_K, Cout, 0, _F(0.0), ptr(slab), cur_stream())
-            elif fused_red is not None:
-                slab = fused_red
-            else:
-                slab = torch.empty((P + rps - 1) // rps, 2, Cout, dtype=torch.float32, device=dev)
-                call("prifit_bn_relu_bwd_reduce", ptr(G_in), _LL(G_in.stride(0)), ptr(Y), _LL(Cout), ptr(scale),
-                     ptr(shift), ptr(mean), ptr(invstd), P, Cout, 0, _F(0.0), ptr(slab), cur_stream())
-            call("prifit_bn_bwd_finalize", ptr(slab), slab.shape[0], Cout, _D(float(P)), int(training), ptr(scale),
-                 ptr(mean), ptr(invstd), ptr(dgamma), ptr(dbeta), ptr(ca), ptr(cb), ptr(cd), cur_stream())
+            dgamma, dbeta, ca, cb, cd = _bwd_coefficients(st, sv, Cout, pooled, G_in, fused_red)
             route = _backward_route(
-                l, L, P, Cout, Kin, pool_K, training, mode, needs[2 + 6 * l], needs[0],
+                l, L, P, Cout, Kin, pool_K, training, st.mode, needs[2 + 6 * l], needs[0],
                 g_dense=G_in.stride(0) == Cout and G_in.data_ptr() % 16 == 0, g_contig=G_in.is_contiguous(),
-                below_ld4=l > 0 and Ys[l - 1] is not None and Ys[l - 1].stride(0) % 4 == 0,
-                N0=front.N if mode == "gather" else 0)
+                below_ld4=l > 0 and below.Y is not None and below.Y.stride(0) % 4 == 0,
+                N0=front.N if st.mode == "gather" else 0)
             wo, wn, bo, nb = wslots.get(l, (0, 0, 0, 0))
-            Yp, aff_p, stats_p = (Ys[l - 1], affines[l - 1], stats_saved[l - 1]) if l > 0 else (x, None, None)
-            ly = types.SimpleNamespace(
-                P=P, Cout=Cout, Kin=Kin, dev=dev, pooled=pooled, pool_K=pool_K, arg=arg, G=G_in, Y=Y, W=W, scale=scale, shift=shift,
-                ca=ca, cb=cb, cd=cd, Yp=Yp, aff_p=aff_p, stats_p=stats_p, front=front, bias0=ctx.bias0,
+            Yp, aff_p, stats_p = (below.Y, (below.scale, below.shift), (below.mean, below.invstd)) if l > 0 else (st.x, None, None)
+            ly = _BwdLayer(
+                P=P, Cout=Cout, Kin=Kin, dev=dev, pooled=pooled, pool_K=pool_K, arg=st.arg, G=G_in, Y=sv.Y, W=sv.W, scale=sv.scale,
+                shift=sv.shift, ca=ca, cb=cb, cd=cd, Yp=Yp, aff_p=aff_p, stats_p=stats_p, front=front, bias0=st.bias0,
                 dW=arena[wo:wo + wn].view(Cout, Kin) if wn else None, need_dW=needs[2 + 6 * l],
                 want_db=needs[3 + 6 * l] and not training)
             G_in, grads[6 * l], fused_red, extra = _ROUTES[route.name](ly, route)
@@ -611,7 +748,7 @@ class SharedMLPFn(torch.autograd.Function):
             grads[6 * l + 2] = dgamma
             grads[6 * l + 3] = dbeta
         # (gather mode: layer 0 took the gather0 route, whose extra is the gradient of Vc, the tensor behind the 6 L layer tensors)
-        return (G_in, None) + tuple(grads) + ((extra,) if mode == "gather" else ())
+        return (G_in, None) + tuple(grads) + ((extra,) if st.mode == "gather" else ())
 
 
 class GatherLinearFn(torch.autograd.Function):

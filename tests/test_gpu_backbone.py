@@ -362,6 +362,139 @@ def test_pool_candidates_match_pool_fwd(nn_ops, P, K, N, Kin):
     assert torch.equal(ystar[nz], want[nz])
 
 
+@pytest.fixture
+def launches(nn_ops, monkeypatch):
+    """The entry points nn_ops launches from here on, by name, in order."""
+    from prifit_amd import _lib
+    seen = []
+
+    def spy(name, *args):
+        seen.append(name)
+        return _lib.call(name, *args)
+
+    monkeypatch.setattr(nn_ops, "call", spy)
+    return seen
+
+
+# case: (P, pool_K, dims, training, (the forward's entry points, the backward's))
+STACK_LAUNCHES = {
+    "a": (32768, 64, ((64, 64), (64, 128)), True, (
+        ["prifit_gemm_stream_f32", "prifit_bn_finalize", "prifit_gemm_stream_pool_f32", "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table", "prifit_gemm_stream_tn_pool_f32",
+         "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_stream_tn_f32",
+         "prifit_gemm_stream_f32"])),
+    "a_three_layers": (32768, 64, ((64, 64), (64, 64), (64, 128)), True, (
+        ["prifit_gemm_stream_f32", "prifit_bn_finalize", "prifit_gemm_stream_f32", "prifit_bn_finalize", "prifit_gemm_stream_pool_f32",
+         "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table", "prifit_gemm_stream_tn_pool_f32",
+         "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_gemm_stream_bwd_f32", "prifit_bn_bwd_finalize",
+         "prifit_bn_relu_bwd_apply", "prifit_gemm_stream_tn_f32", "prifit_gemm_stream_f32"])),
+    "b": (6144, 32, ((64, 196), (196, 256)), True, (
+        ["prifit_gemm_f32", "prifit_bn_finalize", "prifit_gemm_f32", "prifit_bn_finalize", "prifit_pool_fwd"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_apply", "prifit_gemm_f32", "prifit_gemm_dgrad_bnred_f32",
+         "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_f32", "prifit_gemm_f32"])),
+    "b_persistent": (69632, 32, ((64, 196), (196, 256)), True, (
+        ["prifit_gemm_f32", "prifit_bn_finalize", "prifit_gemm_pool_f32", "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_apply", "prifit_gemm_f32", "prifit_gemm_dgrad_bnred_f32",
+         "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_f32", "prifit_gemm_f32"])),
+    "c": (1024, 0, ((516, 256), (256, 512)), True, (
+        ["prifit_gemm_f32", "prifit_bn_finalize", "prifit_gemm_f32", "prifit_bn_finalize", "prifit_affine_relu"],
+        ["prifit_bn_relu_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_f32", "prifit_gemm_dgrad_bnred_f32",
+         "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_f32", "prifit_gemm_f32"])),
+    "d": (32768, 64, ((64, 64), (64, 128)), False, (
+        ["prifit_gemm_stream_f32", "prifit_gemm_stream_f32", "prifit_pool_fwd"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_apply", "prifit_gemm_stream_tn_f32", "prifit_gemm_stream_dgrad_f32",
+         "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_stream_tn_f32", "prifit_gemm_stream_f32"])),
+}
+
+
+@pytest.mark.parametrize("case", sorted(STACK_LAUNCHES))
+def test_shared_mlp_launch_lists(nn_ops, launches, case):
+    """The entry points of one SharedMLPFn forward + backward, in order: the rows of the two tables of DESIGN 3.1 at the
+    smallest shapes that take each arm.  a: 32768 rows, the streaming kernels' floor -- `gemm`, `stream_pool`; `pool` (`pair`),
+    `plain` (`gemm`); a_three_layers: a middle layer on `bn` (`one_pass`).  b: 48 x 2 tiles, below the persistent tiled kernel's
+    512: `gemm` and prifit_pool_fwd; `plain` (`tiled`); b_persistent: 544 x 2 tiles, `tiled_pool`.  c: no pool.  d: a in eval
+    mode (`eval`, no finalize launches; the bias gradients are torch sums)."""
+    P, K, dims, training, want = STACK_LAUNCHES[case]
+    x = _rand((P, dims[0][0]), 31).cuda().requires_grad_(True)
+    g = torch.Generator().manual_seed(32)
+    tens = []
+    for cin, cout in dims:
+        tens += [(torch.randn(cout, cin, generator=g) * (2.0 / cin ** 0.5)).cuda().requires_grad_(True),
+                 torch.zeros(cout, device="cuda", requires_grad=True),
+                 (torch.rand(cout, generator=g) + 0.5).cuda().requires_grad_(True), (torch.randn(cout, generator=g) * 0.1).cuda().requires_grad_(True),
+                 torch.zeros(cout, device="cuda"), torch.ones(cout, device="cuda")]
+    cfg = {"pool_K": K, "training": training, "eps": 1e-5, "momentum": [0.1] * len(dims)}
+    out = nn_ops.SharedMLPFn.apply(x, cfg, *tens)
+    nfwd = len(launches)
+    grads = torch.autograd.grad(out, [x] + [t for t in tens if t.requires_grad], _rand(tuple(out.shape), 33).cuda())
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(t).all() for t in (out,) + grads)
+    assert (launches[:nfwd], launches[nfwd:]) == want
+
+
+FRONT_LAUNCHES = {
+    "direct": (
+        ["prifit_sa_group_linear_fwd", "prifit_bn_finalize", "prifit_gemm_stream_f32", "prifit_bn_finalize", "prifit_gemm_stream_pool_f32",
+         "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table", "prifit_gemm_stream_tn_pool_f32",
+         "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_gemm_stream_bwd_f32", "prifit_bn_bwd_finalize",
+         "prifit_sa_first_layer_dw_bn", "prifit_slab_sum"]),
+    "preact": (
+        ["prifit_sa_group_linear_fwd", "prifit_bn_finalize", "prifit_gemm_stream_f32", "prifit_bn_finalize", "prifit_gemm_stream_pool_f32",
+         "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table", "prifit_gemm_stream_tn_pool_f32",
+         "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_gemm_stream_bwd_f32", "prifit_bn_bwd_finalize",
+         "prifit_bn_relu_bwd_apply", "prifit_sa_first_layer_dw", "prifit_slab_sum"]),
+    "gather": (
+        ["prifit_gemm_f32", "prifit_gemm_f32", "prifit_sa_group_linear_fwd", "prifit_bn_finalize", "prifit_gemm_f32", "prifit_bn_finalize",
+         "prifit_gemm_f32", "prifit_bn_finalize", "prifit_pool_fwd"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_apply", "prifit_gemm_f32", "prifit_gemm_dgrad_bnred_f32",
+         "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply", "prifit_gemm_f32", "prifit_gemm_dgrad_bnred_f32", "prifit_bn_bwd_finalize",
+         "prifit_list_csr", "prifit_gather_linear_bwd_csr", "prifit_gemm_f32", "prifit_gemm_f32", "prifit_gemm_f32"]),
+    "norows": (
+        ["prifit_sa_point_tables", "prifit_sa_group_linear_fwd", "prifit_bn_finalize", "prifit_gemm_f32", "prifit_bn_finalize", "prifit_gemm_f32",
+         "prifit_bn_finalize", "prifit_pool_fwd", "prifit_bn_finalize", "prifit_gemm_stream_gather_f32", "prifit_bn_finalize",
+         "prifit_gemm_stream_pool_f32", "prifit_bn_finalize", "prifit_pool_from_candidates", "prifit_bn_finalize", "prifit_gemm_stream_gather_f32",
+         "prifit_bn_finalize", "prifit_gemm_stream_pool_f32", "prifit_bn_finalize", "prifit_pool_from_candidates"],
+        ["prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table", "prifit_gemm_stream_tn_pool_f32",
+         "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_gemm_stream_bwd_gather_f32", "prifit_bn_bwd_finalize",
+         "prifit_sa_first_layer_dw_bn_gather", "prifit_slab_sum", "prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize", "prifit_pool_bwd_table",
+         "prifit_gemm_stream_tn_pool_f32", "prifit_gemm_stream_dgrad_pool_f32", "prifit_bn_bwd_finalize", "prifit_gemm_stream_bwd_gather_f32",
+         "prifit_bn_bwd_finalize", "prifit_sa_first_layer_dw_bn_gather", "prifit_slab_sum", "prifit_pool_bwd_reduce", "prifit_bn_bwd_finalize",
+         "prifit_pool_bwd_apply", "prifit_gemm_stream_tn_f32", "prifit_gemm_dgrad_bnred_f32", "prifit_bn_bwd_finalize", "prifit_bn_relu_bwd_apply",
+         "prifit_gemm_stream_tn_f32", "prifit_gemm_dgrad_bnred_f32", "prifit_bn_bwd_finalize", "prifit_sa_first_layer_dw_bn", "prifit_slab_sum"]),
+}
+
+
+@pytest.mark.parametrize("mode", sorted(FRONT_LAUNCHES))
+def test_sa_level_launch_lists_per_front_mode(nn_ops, launches, monkeypatch, mode):
+    """The same for one set-abstraction level per FrontEnd.mode (DESIGN 3.2 for the front end's own launches, 3.1 for the
+    stacks'), at the smallest configurations of tests/test_gpu_sa_fused.py that take the mode."""
+    from prifit_amd.models import pointnet_util as pu
+    if mode in ("direct", "preact"):          # no features: direct; its autograd arm hands the stack a pre-activation
+        xyz, feats = _t(synth.cloud("surface", 4, 1024, 4)).cuda(), None
+        make = lambda: pu.PointNetSetAbstraction(128, 0.4, 64, 3, [64, 64, 128], False)
+        monkeypatch.setattr(pu, "_DIRECT_FUSED_BWD", mode == "direct")
+    elif mode == "gather":                     # 96 feature channels that want a gradient, ragged N
+        xyz = _t(synth.cloud("cube", 3, 300, 5)).cuda()
+        feats = torch.randn(3, 300, 96, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)).requires_grad_(True)
+        make = lambda: pu.PointNetSetAbstraction(64, 0.3, 32, 96 + 3, [64, 64, 128], False)
+    else:                                      # norows: the multi-scale module, its two 64-wide scales unstored
+        xyz = _t(synth.cloud("surface", 3, 2048, 1)).cuda()
+        feats = xyz
+        make = lambda: pu.PointNetSetAbstractionMsg(512, [0.1, 0.2, 0.4], [32, 64, 128], 3, [[32, 32, 64], [64, 64, 128], [64, 96, 128]])
+        monkeypatch.setattr(pu, "_SA_NOROWS", True)
+    torch.manual_seed(7)
+    m = make().cuda().train()
+    _, out = m.forward_cl(xyz, feats, fps_start=torch.zeros(xyz.shape[0], dtype=torch.long, device="cuda"))
+    nfwd = len(launches)
+    (out * _rand(tuple(out.shape), 3).cuda()).sum().backward()
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(p.grad).all() for p in m.parameters())
+    assert (launches[:nfwd], launches[nfwd:]) == FRONT_LAUNCHES[mode]
+
+
 def _run_pair(my, orc_mod, args_gpu, args_cpu, gout, n_out=1, pick=lambda o: o):
     """Run the HIP module and the oracle module with identical parameters; return outputs+grads."""
     my.load_state_dict(orc_mod.state_dict())
