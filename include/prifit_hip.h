@@ -35,7 +35,7 @@ extern "C" {
 /* Library identification: returns PRIFIT_ABI_VERSION (10000*major + 100*minor + patch) of the header the library was built
  * from; *arch (may be NULL) receives a static string naming the code object target ("gfx950").  The minor number goes up
  * whenever an entry point's parameter list changes: ctypes passes arguments by position and cannot tell. */
-#define PRIFIT_ABI_VERSION 804
+#define PRIFIT_ABI_VERSION 805
 int prifit_version(const char **arch);
 
 /* ------------------------------------------------------------------------------------------ */
@@ -1102,6 +1102,33 @@ int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0
                               int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
                               float *workspace, void *stream);
 
+/* The per-point embedding of the part-segmentation network in one launch (FrozenPartSeg.embed):
+ * extra_conv_emb(relu(bn1(conv1(fp1(...))))) of models/pointnet2_part_seg_msg.py:119-130 in eval mode, optionally
+ * unit-normalised, and -- from the same registers -- the scores / labels of prifit_mlp_chain_rows_f32.  X [P, ldx] raw rows,
+ * K0 wide; layers 1 .. 3 exactly as in prifit_mlp_chain_rows_f32 give a_3 (the network's `feat`), then two heads:
+ *   head B (always): e = W_e a_3 + b_e, 128 channels, no ReLU -> emb [P, lde] row-major, 16-byte aligned, lde >= 128 and
+ *     lde % 4 == 0; columns 128 .. lde - 1 are not written.  normalize != 0: e / max(||e||_2, 1e-12) (F.normalize(e, p=2,
+ *     dim=channel)): the squares are summed in fp32 in a fixed order (csrc/infer_chain.h), square root and division are
+ *     correctly rounded; a NaN anywhere in a row's e makes that whole row NaN and touches no other row.
+ *   head A (CL > 0): z = W_cls a_3 + b_cls, W_cls [CL, ldw_cls], 1 <= CL <= 64 -> scores [P, lds] and / or labels [P] with
+ *     cat_of_label / shape_cat / rows_per_shape, all as in prifit_mlp_chain_rows_f32 and equal to its results on the same
+ *     operands bit for bit (the same code in the same order).  CL == 0: no head A; W_cls, b_cls, scores, labels NULL.
+ * W, ldw, b: HOST arrays of L = 4 entries, read before the call returns: layers 1 .. 3, then W_e [128, ldw_4] / b_e.
+ * No [P, 128] tensor but emb is written: a wave keeps its 32 rows in registers from the load to both heads.
+ * prifit_mlp_chain_embed_supported: 1 for L == 4, widths (128, 128, 128, 128), K0 % 8 == 0, 8 <= K0 <= 160 and CL == 0 or
+ * 1 <= CL <= 64; 0 otherwise.  prifit_mlp_chain_embed_workspace: floats of `workspace` (0 today: workspace may be NULL).
+ * PRIFIT_EINVAL without a launch: an unsupported shape; whatever prifit_mlp_chain_rows_f32 rejects of its own arguments (X,
+ * ldx, P, W, ldw, b, lds, cat_of_label / shape_cat, rows_per_shape); emb NULL or not 16-byte aligned; lde < 128 or not a
+ * multiple of 4; scores or labels given with CL == 0; CL > 0 with W_cls or b_cls NULL or misaligned, ldw_cls < 128 or not a
+ * multiple of 4, or with neither scores nor labels. */
+int prifit_mlp_chain_embed_supported(int K0, int L, const int32_t *widths, int CL);
+long long prifit_mlp_chain_embed_workspace(long long P, int K0, int L, const int32_t *widths, int CL);
+int prifit_mlp_chain_embed_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                               const float *const *W, const long long *ldw, const float *const *b, const float *W_cls,
+                               long long ldw_cls, const float *b_cls, int CL, float *emb, long long lde, int normalize,
+                               float *scores, long long lds, int32_t *labels, const int32_t *cat_of_label,
+                               const int32_t *shape_cat, int rows_per_shape, float *workspace, void *stream);
+
 /* The training half of that tail, for pre-training the classifier layer on the frozen network (train_partseg_shapenet.py:56-99,
  * FrozenPartSeg.probe_step): the same four layers over raw rows X [P, ldx] -- layers 1 .. 3 exactly as in
  * prifit_mlp_chain_rows_f32, z = W_4 a_3 + b_4 with C_L = widths[3] <= 64 -- ending in the segmentation loss, the gradient of
@@ -1172,6 +1199,19 @@ int prifit_mlp_chain_rows_bf16(const float *X, long long ldx, long long P, int K
                                const uint16_t *const *W, const long long *ldw, const float *const *b, float *scores, long long lds,
                                int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape,
                                float *workspace, void *stream);
+
+/* prifit_mlp_chain_embed_f32 with bf16 products: the same contract and the same PRIFIT_EINVAL cases, the rules of
+ * prifit_mlp_chain_rows_bf16 for the operands -- W_1 bf16 in the plain order, W_2, W_3, W_e and W_cls in the accumulator
+ * order as prifit_pack_bf16_multi writes them (ldw >= the input width rounded up to 16, multiples of 8 elements, 16-byte
+ * aligned); b, b_e and b_cls fp32.  a_3 is rounded to bf16 once and feeds both heads; emb is the fp32 accumulators of head B
+ * plus b_e, and the normalisation runs on them in fp32 exactly as in the fp32 entry point. */
+int prifit_mlp_chain_embed_bf16_supported(int K0, int L, const int32_t *widths, int CL);
+long long prifit_mlp_chain_embed_bf16_workspace(long long P, int K0, int L, const int32_t *widths, int CL);
+int prifit_mlp_chain_embed_bf16(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                                const uint16_t *const *W, const long long *ldw, const float *const *b, const uint16_t *W_cls,
+                                long long ldw_cls, const float *b_cls, int CL, float *emb, long long lde, int normalize,
+                                float *scores, long long lds, int32_t *labels, const int32_t *cat_of_label,
+                                const int32_t *shape_cat, int rows_per_shape, float *workspace, void *stream);
 
 #ifdef __cplusplus
 }

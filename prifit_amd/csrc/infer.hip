@@ -6,8 +6,9 @@
 //   fold_bn_kernel         every layer of a network in ONE launch: W' = W * s, b' = (b - mean) * s + beta, s = gamma / sqrt(var + eps)
 //   mlp_chain_pool_kernel  layers 2 and 3 of a scale and its pool in one launch, the intermediates in registers
 //   mlp_chain_rows_kernel  the per-point tail (fp1, conv1 + bn1, conv2) and the restricted arg-max in one launch
+//   mlp_chain_embed_kernel the same tail with two heads: extra_conv_emb (row-major, optionally unit-normalised) and conv2
 //
-// The two chain kernels, their argument checks and their launch ladders are written once, in infer_chain.h, over a matrix-pipe
+// The chain kernels, their argument checks and their launch ladders are written once, in infer_chain.h, over a matrix-pipe
 // policy; this file holds the fold and the fp32 entry points, which instantiate the skeleton for the fp32 policy (PipeF32 of
 // infer_pipe_f32.h: v_mfma_f32_32x32x2_f32, exact fp32, the instruction of gemm.hip and gemm_stream.hip).  The bf16 twin is
 // infer_bf16.hip; the training half of the row chain (loss and conv2 gradient) is probe_head.hip.
@@ -116,6 +117,20 @@ int prifit_mlp_chain_rows_f32(const float *X, long long ldx, long long P, int K0
 {
     return chain_rows_run<PipeF32>(X, ldx, P, K0, L, widths, W, ldw, b, scores, lds, labels, cat_of_label, shape_cat, rows_per_shape,
                                    stream);
+}
+
+int prifit_mlp_chain_embed_supported(int K0, int L, const int32_t *widths, int CL) { return chain_embed_supported(K0, L, widths, CL); }
+
+long long prifit_mlp_chain_embed_workspace(long long, int, int, const int32_t *, int) { return 0; }     // likewise
+
+int prifit_mlp_chain_embed_f32(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                               const float *const *W, const long long *ldw, const float *const *b, const float *W_cls,
+                               long long ldw_cls, const float *b_cls, int CL, float *emb, long long lde, int normalize, float *scores,
+                               long long lds, int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat,
+                               int rows_per_shape, float *, void *stream)
+{
+    return chain_embed_run<PipeF32>(X, ldx, P, K0, L, widths, W, ldw, b, W_cls, ldw_cls, b_cls, CL, emb, lde, normalize, scores, lds,
+                                    labels, cat_of_label, shape_cat, rows_per_shape, stream);
 }
 
 }  // extern "C"

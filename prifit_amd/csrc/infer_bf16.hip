@@ -144,4 +144,21 @@ int prifit_mlp_chain_rows_bf16(const float *X, long long ldx, long long P, int K
                                     stream);
 }
 
+int prifit_mlp_chain_embed_bf16_supported(int K0, int L, const int32_t *widths, int CL)
+{
+    return chain_embed_supported(K0, L, widths, CL);
+}
+
+long long prifit_mlp_chain_embed_bf16_workspace(long long, int, int, const int32_t *, int) { return 0; }     // likewise
+
+int prifit_mlp_chain_embed_bf16(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths,
+                                const uint16_t *const *W, const long long *ldw, const float *const *b, const uint16_t *W_cls,
+                                long long ldw_cls, const float *b_cls, int CL, float *emb, long long lde, int normalize, float *scores,
+                                long long lds, int32_t *labels, const int32_t *cat_of_label, const int32_t *shape_cat,
+                                int rows_per_shape, float *, void *stream)
+{
+    return chain_embed_run<PipeBf16>(X, ldx, P, K0, L, widths, W, ldw, b, W_cls, ldw_cls, b_cls, CL, emb, lde, normalize, scores, lds,
+                                     labels, cat_of_label, shape_cat, rows_per_shape, stream);
+}
+
 }  // extern "C"

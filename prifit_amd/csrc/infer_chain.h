@@ -15,9 +15,10 @@
 //   mma(a, b, acc)   the MFMA(s) of one k-step
 //   block_end()      a scheduling hook behind a finished block's fragments (bf16: a fence, see PipeBf16)
 //   pitch_ok(ld, kin)   (host) the pitch rule of a weight row
-// Everything else is here: the product of one output block, bias + ReLU, the two kernels, what follows the last product (the
-// max over a wave's rows and the pooling groups of a workgroup; the scores' stores and the category-restricted arg-max), the
-// argument checks and the launch ladders.  Each of the two translation units instantiates the kernels for its own pipe.
+// Everything else is here: the product of one output block, bias + ReLU, the three kernels (pooled chain, row chain, embedding
+// chain), what follows the last product (the max over a wave's rows and the pooling groups of a workgroup; the scores' stores
+// and the category-restricted arg-max; the embedding's stores and its normalisation), the argument checks and the launch
+// ladders.  Each of the two translation units instantiates the kernels for its own pipe.
 #pragma once
 #include "common.h"
 
@@ -411,25 +412,199 @@ void chain_rows_dispatch(int kq, const RowsArgsT<typename Pipe::W> &g, hipStream
     } else if constexpr (KQ > 1) chain_rows_dispatch<Pipe, KQ - 1>(kq, g, st);
 }
 
+// the argument checks of the row chain, shared by its consumers (the labels' chain, the embedding chain): everything about
+// the rows, the four layers' host arrays and the scores / labels outputs -> g, PRIFIT_EINVAL for what they refuse.  The
+// shape query is the caller's; CL is the width of the product that feeds scores / labels (its layer may be none of W's).
+template <typename Pipe>
+int chain_rows_args(RowsArgsT<typename Pipe::W> &g, const float *X, long long ldx, long long P, int K0, const typename Pipe::W *const *W,
+                    const long long *ldw, const float *const *b, int CL, float *scores, long long lds, int32_t *labels,
+                    const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape)
+{
+    if (!X || !W || !ldw || !b || P < 1 || P > 0x7fffffffLL || ldx < K0 || (ldx & 3) || mis16(X) || rows_per_shape <= 0)
+        return PRIFIT_EINVAL;
+    if (scores && lds < CL) return PRIFIT_EINVAL;
+    if (labels && (shape_cat != nullptr) != (cat_of_label != nullptr)) return PRIFIT_EINVAL;
+    if (labels && shape_cat && P % rows_per_shape) return PRIFIT_EINVAL;
+    for (int l = 0; l < ROWS_L; ++l) {
+        if (!W[l] || !b[l] || !Pipe::pitch_ok(ldw[l], l ? ROWS_W : K0) || mis16(W[l]) || mis16(b[l])) return PRIFIT_EINVAL;
+        g.W[l] = W[l]; g.b[l] = b[l]; g.ldw[l] = ldw[l];
+    }
+    g.X = X; g.ldx = ldx; g.P = P; g.CL = CL; g.scores = scores; g.lds = lds; g.labels = labels;
+    g.cat_of_label = labels ? cat_of_label : nullptr; g.shape_cat = labels ? shape_cat : nullptr; g.N = rows_per_shape;
+    return PRIFIT_OK;
+}
+
 template <typename Pipe>
 int chain_rows_run(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths, const typename Pipe::W *const *W,
                    const long long *ldw, const float *const *b, float *scores, long long lds, int32_t *labels,
                    const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape, void *stream)
 {
-    if (!chain_rows_supported(K0, L, widths) || !X || !W || !ldw || !b || (!scores && !labels) || P < 1 || P > 0x7fffffffLL ||
-        ldx < K0 || (ldx & 3) || mis16(X) || rows_per_shape <= 0)
-        return PRIFIT_EINVAL;
-    if (scores && lds < widths[ROWS_L - 1]) return PRIFIT_EINVAL;
-    if (labels && (shape_cat != nullptr) != (cat_of_label != nullptr)) return PRIFIT_EINVAL;
-    if (labels && shape_cat && P % rows_per_shape) return PRIFIT_EINVAL;
+    if (!chain_rows_supported(K0, L, widths) || (!scores && !labels)) return PRIFIT_EINVAL;
     RowsArgsT<typename Pipe::W> g = {};
-    for (int l = 0; l < ROWS_L; ++l) {
-        if (!W[l] || !b[l] || !Pipe::pitch_ok(ldw[l], l ? ROWS_W : K0) || mis16(W[l]) || mis16(b[l])) return PRIFIT_EINVAL;
-        g.W[l] = W[l]; g.b[l] = b[l]; g.ldw[l] = ldw[l];
-    }
-    g.X = X; g.ldx = ldx; g.P = P; g.CL = widths[ROWS_L - 1]; g.scores = scores; g.lds = lds; g.labels = labels;
-    g.cat_of_label = labels ? cat_of_label : nullptr; g.shape_cat = labels ? shape_cat : nullptr; g.N = rows_per_shape;
+    if (chain_rows_args<Pipe>(g, X, ldx, P, K0, W, ldw, b, widths[ROWS_L - 1], scores, lds, labels, cat_of_label, shape_cat,
+                              rows_per_shape))
+        return PRIFIT_EINVAL;
     chain_rows_dispatch<Pipe, ROWS_MAX_K0 / 8>(K0 / 8, g, as_stream(stream));
+    return prifit_check_launch();
+}
+
+// ---- the per-point embedding: layers 1 .. 3 of the row chain, then TWO heads on a_3 (the network's `feat`) while it is in
+// registers -- head A, the row chain's last layer and emit code (scores and / or labels; optional), and head B,
+// e = W_e a_3 + b_e, 128 channels, no ReLU (extra_conv_emb), stored row-major: lane (j, h) writes its four channels
+// 32b + 8g + 4h + 0 .. 3 of row j as one 16-byte store, so a row is written as 16-byte pieces, two adjacent ones per store
+// instruction (the scores' pattern).
+//
+// NORM (F.normalize(e, p = 2, dim = channel)): the four head-B blocks stay in accumulators (hb is dead by then).  The order of
+// the sum of squares is fixed: lane (j, h) adds the squares of its 64 values to 0 in the order block 0 .. 3, register 0 .. 15
+// (channel 32b + 8(r >> 2) + 4h + (r & 3)), one rounded multiply and one rounded add each, no fma; then ONE exchange with
+// lane (j, 1 - h), s = own + other -- fp32 addition commutes, so both lanes hold the same bits.  Then sqrt and divide, each
+// correctly rounded: e / max(sqrt(s), 1e-12).  A NaN in s makes the divisor NaN (torch's clamp_min keeps it), so the whole
+// row is NaN; no other row sees it.
+template <typename WT>
+struct EmbedArgsT {
+    RowsArgsT<WT> r;         // X, layers 1 .. 3 in W/b/ldw[0 .. 2]; head A in W/b/ldw[3], CL (0: no head A), scores, labels ...
+    const WT *We;
+    const float *be;
+    long long ldwe;
+    float *emb;
+    long long lde;
+};
+
+// head B's bias on the finished block b
+__device__ __forceinline__ void embed_bias(f32x16 &acc, const float *__restrict__ be, int b, int lh)
+{
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const float4 bb = ld4(be + 32 * b + 8 * gq + 4 * lh);
+        acc[4 * gq + 0] += bb.x; acc[4 * gq + 1] += bb.y; acc[4 * gq + 2] += bb.z; acc[4 * gq + 3] += bb.w;
+    }
+}
+
+// s + a a in two roundings whatever -ffp-contract says: the sum of squares has a stated order AND stated roundings
+__device__ __forceinline__ float embed_sq_add(float s, float a)
+{
+#pragma clang fp contract(off)
+    const float q = a * a;
+    return s + q;
+}
+
+__device__ __forceinline__ void embed_store(const f32x16 &acc, float *er, int b, int lh)
+{
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+        *reinterpret_cast<float4 *>(er + 32 * b + 8 * gq + 4 * lh) =
+            make_float4(acc[4 * gq + 0], acc[4 * gq + 1], acc[4 * gq + 2], acc[4 * gq + 3]);
+}
+
+template <typename Pipe, int KQ, bool NORM>
+__global__ __launch_bounds__(256) void mlp_chain_embed_kernel(const EmbedArgsT<typename Pipe::W> e)
+{
+    constexpr int K0 = 8 * KQ, H = Pipe::KSTEP / 2;
+    const RowsArgsT<typename Pipe::W> &g = e.r;
+    __shared__ int s_cat[ROWS_MAX_CL];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int li = lane & 31, lh = lane >> 5;
+    const int CL = g.CL;
+    rows_load_cats(g, s_cat);
+    const long long row0 = (long long)blockIdx.x * CHAIN_ROWS + 32 * wave;
+    if (row0 >= g.P) return;                      // wave-uniform
+    const long long row = row0 + li;
+    const bool live = row < g.P;                  // a row past the end computes on a copy of the last row and stores nothing
+    const long long rowc = live ? row : g.P - 1;
+
+    typename Pipe::Frag ha[chain_ksteps<Pipe>(ROWS_W)], hb[chain_ksteps<Pipe>(ROWS_W)];
+    {
+        typename Pipe::Frag xf[chain_ksteps<Pipe>(K0)];
+        const float *xr = g.X + rowc * g.ldx + H * lh;
+#pragma unroll
+        for (int t = 0; t < chain_ksteps<Pipe>(K0); ++t) xf[t] = Pipe::template from_mem<false, K0>(xr, t, lh);
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b)
+            chain_close<Pipe, true, ROWS_W>(chain_block<Pipe, K0, false>(g.W[0], g.ldw[0], b, ROWS_W, xf, li, lh), g.b[0], b, lh, ha);
+    }
+    chain_rows_layer<Pipe>(g.W[1], g.ldw[1], g.b[1], ha, hb, li, lh);
+    chain_rows_layer<Pipe>(g.W[2], g.ldw[2], g.b[2], hb, ha, li, lh);
+
+    // head A: the row chain's layer 4 and emit code (grid-uniform: present or not)
+    if (CL > 0) {
+        RowsRank rk = rows_rank_begin(g, rowc);
+#pragma unroll
+        for (int b2 = 0; b2 < ROWS_MAX_CL / 32; ++b2) {
+            if (32 * b2 >= CL) break;
+            rows_emit(g, chain_block<Pipe, ROWS_W, true>(g.W[3], g.ldw[3], b2, CL, ha, li, lh), b2, lh, row, live, s_cat, rk);
+        }
+        rows_finish(g, rk, lh, row, live);
+    }
+
+    // head B
+    float *er = e.emb + row * e.lde;
+    if constexpr (!NORM) {
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {       // a block is stored as it finishes: nothing is kept
+            f32x16 acc = chain_block<Pipe, ROWS_W, false>(e.We, e.ldwe, b, ROWS_W, ha, li, lh);
+            embed_bias(acc, e.be, b, lh);
+            if (live) embed_store(acc, er, b, lh);
+            Pipe::block_end();
+        }
+    } else {
+        f32x16 acc[ROWS_NB];
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {
+            acc[b] = chain_block<Pipe, ROWS_W, false>(e.We, e.ldwe, b, ROWS_W, ha, li, lh);
+            embed_bias(acc[b], e.be, b, lh);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s = embed_sq_add(s, acc[b][r]);
+        s += __shfl_xor(s, 32);                   // every lane of the wave is here: rows past the end compute too
+        // sqrtf and / are correctly rounded in a HIP build (no -ffast-math, no -fno-hip-fp32-correctly-rounded-divide-sqrt;
+        // __fsqrt_rn is NOT: without OCML_BASIC_ROUNDED_OPERATIONS it is the hardware's approximate square root)
+        const float q = __builtin_sqrtf(s);
+        const float d = q < 1e-12f ? 1e-12f : q;  // fmaxf(q, 1e-12f) for a number; a NaN stays (fmaxf would drop it)
+#pragma unroll
+        for (int b = 0; b < ROWS_NB; ++b) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[b][r] = acc[b][r] / d;
+            if (live) embed_store(acc[b], er, b, lh);
+        }
+    }
+}
+
+// widths (128, 128, 128, 128): layers 1 .. 3 and W_e; CL == 0: no head A
+inline int chain_embed_supported(int K0, int L, const int32_t *widths, int CL)
+{
+    if (L != ROWS_L || !widths || widths[ROWS_L - 1] != ROWS_W || CL < 0) return 0;
+    const int32_t as_rows[ROWS_L] = {widths[0], widths[1], widths[2], CL ? CL : 1};
+    return chain_rows_supported(K0, L, as_rows);
+}
+
+template <typename Pipe, int KQ>
+void chain_embed_dispatch(int kq, bool norm, const EmbedArgsT<typename Pipe::W> &e, hipStream_t st)
+{
+    if (kq == KQ) {
+        const dim3 grid((unsigned)((e.r.P + CHAIN_ROWS - 1) / CHAIN_ROWS));
+        if (norm) hipLaunchKernelGGL((mlp_chain_embed_kernel<Pipe, KQ, true>), grid, dim3(256), 0, st, e);
+        else hipLaunchKernelGGL((mlp_chain_embed_kernel<Pipe, KQ, false>), grid, dim3(256), 0, st, e);
+    } else if constexpr (KQ > 1) chain_embed_dispatch<Pipe, KQ - 1>(kq, norm, e, st);
+}
+
+template <typename Pipe>
+int chain_embed_run(const float *X, long long ldx, long long P, int K0, int L, const int32_t *widths, const typename Pipe::W *const *W,
+                    const long long *ldw, const float *const *b, const typename Pipe::W *W_cls, long long ldw_cls, const float *b_cls,
+                    int CL, float *emb, long long lde, int normalize, float *scores, long long lds, int32_t *labels,
+                    const int32_t *cat_of_label, const int32_t *shape_cat, int rows_per_shape, void *stream)
+{
+    if (!chain_embed_supported(K0, L, widths, CL) || !emb || mis16(emb) || lde < ROWS_W || (lde & 3)) return PRIFIT_EINVAL;
+    if ((CL > 0) != (scores || labels)) return PRIFIT_EINVAL;      // head A: asked for and described, or neither
+    if (CL > 0 && (!W_cls || !b_cls || !Pipe::pitch_ok(ldw_cls, ROWS_W) || mis16(W_cls) || mis16(b_cls))) return PRIFIT_EINVAL;
+    EmbedArgsT<typename Pipe::W> e = {};
+    if (chain_rows_args<Pipe>(e.r, X, ldx, P, K0, W, ldw, b, CL, scores, lds, labels, cat_of_label, shape_cat, rows_per_shape))
+        return PRIFIT_EINVAL;
+    e.We = e.r.W[3]; e.be = e.r.b[3]; e.ldwe = e.r.ldw[3]; e.emb = emb; e.lde = lde;
+    e.r.W[3] = W_cls; e.r.b[3] = b_cls; e.r.ldw[3] = ldw_cls;
+    chain_embed_dispatch<Pipe, ROWS_MAX_K0 / 8>(K0 / 8, normalize != 0, e, as_stream(stream));
     return prifit_check_launch();
 }
 

@@ -5,6 +5,7 @@
     seg, (l1, l2, l3), feat, zero, zero = frozen(xyz, cls_label, fps_start=None)
     seg = frozen.predict(xyz, cls_label)             # [B, N, num_parts] log-probabilities
     part = frozen.labels(xyz, cls_label, shape_cat, cat_of_label)   # [B, N] int32 part labels, one launch for the tail
+    emb = frozen.embed(xyz, cls_label)               # [B, N, 128] per-point embedding, row-major, one launch for the tail (3.9.4)
     loss_kept_correct = frozen.probe_step(xyz, cls_label, target)   # --init_cls: loss + conv2's gradient in one launch pair (3.9.3)
     frozen.refresh()                                 # re-fold from the live model (after more training)
 
@@ -19,14 +20,18 @@ The forward then runs on that buffer alone, under no_grad:
   * SA3, the feature-propagation stacks and the head: one folded product per layer on prifit_gemm_f32 (bias, ReLU on load
     through a unit-scale a_affine), then the existing pool / affine launch;
   * labels() only: fp1, conv1 + bn1, conv2 and the category-restricted arg-max in one launch (prifit_mlp_chain_rows_f32).
+  * embed() only: fp1, conv1 + bn1, then extra_conv_emb (optionally F.normalize) and -- with return_labels -- conv2 and the
+    arg-max on the same registers, one launch (prifit_mlp_chain_embed_f32): the embedding the primitive fitting consumes,
+    written once, row-major.  forward(embed=True) keeps its separate launches.
   * probe_step() only: the same chain ending in the segmentation loss, the gradient of the live conv2 and the accuracy count
     (prifit_probe_head_f32) -- the training half of the tail, for pre-training the classifier layer on the frozen network.
 No column statistics, no slabs, no arg-max tensors for a backward, no per-call arithmetic on weights.  There is no fall-back
 to the live model: a shape the kernels do not take is an error.
 
-The two on-chip chains have one driver each (_chain_pool, _chain_rows) over a table keyed by precision (_CHAINS): entry
-point, queries, profiler tag and where a layer's weight lives.  precision="bf16"  changes their arithmetic
-only: prifit_mlp_chain_pool_bf16 and prifit_mlp_chain_rows_bf16 round every layer input to bf16 and accumulate in fp32.  Their
+The on-chip chains have one driver each (_chain_pool, _chain_rows, _chain_embed) over a table keyed by precision (_CHAINS):
+entry point, queries, profiler tag and where a layer's weight lives.  precision="bf16"  changes their arithmetic
+only: prifit_mlp_chain_pool_bf16, prifit_mlp_chain_rows_bf16 and prifit_mlp_chain_embed_bf16 round every layer input to bf16
+and accumulate in fp32.  Their
 weights are a second flat buffer of 16-bit patterns, written by ONE more launch of refresh() (prifit_pack_bf16_multi) in the
 column order the MFMA reads; the biases stay fp32 in `flat`.  Everything else is the fp32 module's, launch for launch."""
 import ctypes
@@ -51,9 +56,11 @@ PRECISIONS = ("fp32", "bf16")
 _CHAINS = {
     "fp32": {"pool": ("prifit_mlp_chain_pool_f32", "prifit_mlp_chain_pool", "mlp_chain_pool"),
              "rows": ("prifit_mlp_chain_rows_f32", "prifit_mlp_chain_rows", "mlp_chain_rows"),
+             "embed": ("prifit_mlp_chain_embed_f32", "prifit_mlp_chain_embed", "mlp_chain_embed"),
              "weight": lambda ly, w: (ly.W, ly.ldw), "pool_fallback": True},
     "bf16": {"pool": ("prifit_mlp_chain_pool_bf16", "prifit_mlp_chain_pool_bf16", "mlp_chain_pool_bf16"),
              "rows": ("prifit_mlp_chain_rows_bf16", "prifit_mlp_chain_rows_bf16", "mlp_chain_rows_bf16"),
+             "embed": ("prifit_mlp_chain_embed_bf16", "prifit_mlp_chain_embed_bf16", "mlp_chain_embed_bf16"),
              "weight": lambda ly, w: (w.W, w.ldk), "pool_fallback": False},
 }
 
@@ -196,7 +203,7 @@ class FrozenPartSeg(nn.Module):
         self.flat = nn.Parameter(flat, requires_grad=False)
         # bf16 only: the chained layers' weights as 16-bit patterns -- an integer buffer, so that .float() / .half() on
         # the module cannot reinterpret it
-        self._bf16 = []
+        self._bf16, self._emb_bf16 = [], []
         if precision == "bf16":
             chained = lambda st: [_Bf16(st[1], st[1].cout, st[1].kin, 0), _Bf16(st[2], st[2].cout, st[2].kin, 1)]
             for lv in self._sa:
@@ -205,11 +212,13 @@ class FrozenPartSeg(nn.Module):
             self._tail_bf16 = [_Bf16(self._tail_w0, self._tail[0].cout, self._tail_kp, 0)] + \
                               [_Bf16(ly, ly.cout, ly.kin, 1) for ly in self._tail[1:]]
             self._bf16 += self._tail_bf16
-            if len(self._bf16) > query("prifit_pack_bf16_max_jobs"):
+            # embed(): extra_conv_emb, fed by conv1 + bn1's registers like conv2 -- a list of its own, the same pack launch
+            self._emb_bf16 = [_Bf16(self._emb, self._emb.cout, self._emb.kin, 1)]
+            if len(self._bf16) + len(self._emb_bf16) > query("prifit_pack_bf16_max_jobs"):
                 raise TypeError("freeze(): %d chained layers, prifit_pack_bf16_multi takes %d"
-                                % (len(self._bf16), query("prifit_pack_bf16_max_jobs")))
+                                % (len(self._bf16) + len(self._emb_bf16), query("prifit_pack_bf16_max_jobs")))
             off16 = 0
-            for w in self._bf16:
+            for w in self._bf16 + self._emb_bf16:
                 w.off, off16 = off16, off16 + (w.cout * w.ldk + _ALIGN16 - 1) // _ALIGN16 * _ALIGN16
             self.register_buffer("flat_bf16", torch.zeros(off16, dtype=torch.int16, device=dev))
         self._bound = None
@@ -235,7 +244,7 @@ class FrozenPartSeg(nn.Module):
             p.W = flat[p.off:p.off + p.layer.cout * len(p.cols)].view(p.layer.cout, len(p.cols))
         self._ones = flat[self._ones_off:self._ones_off + self._unit_c]
         self._zeros = flat[self._zeros_off:self._zeros_off + self._unit_c]
-        for w in self._bf16:
+        for w in self._bf16 + self._emb_bf16:
             w.W = self.flat_bf16[w.off:w.off + w.cout * w.ldk].view(w.cout, w.ldk)
         self._bound = key
         return flat
@@ -280,7 +289,7 @@ class FrozenPartSeg(nn.Module):
                  nn_ops._ptr_array(maps), (ctypes.c_int32 * m)(*[len(p.cols) for p in ps]), nn_ops._ptr_array([p.W for p in ps]),
                  cur_stream())
         if self._bf16:
-            ws = self._bf16
+            ws = self._bf16 + self._emb_bf16
             m = len(ws)
             if self.flat_bf16.device != flat.device:
                 raise RuntimeError("refresh(): flat is on %s, flat_bf16 on %s" % (flat.device, self.flat_bf16.device))
@@ -385,6 +394,55 @@ class FrozenPartSeg(nn.Module):
             scores = torch.empty(B, N, parts, dtype=torch.float32, device=dev) if return_scores else None
             self._chain_rows(rows, K0, widths, scores, out, cat_of_label, shape_cat, N)
         return (out, scores) if return_scores else out
+
+    def _embed_shape(self):
+        """(K0, widths, parts) of the embedding chain -- fp1's two layers, conv1 + bn1, extra_conv_emb, and conv2 as the
+        second head; NotImplementedError where the chain of this precision does not take it."""
+        K0, widths, parts = self._tail_kp, [ly.cout for ly in self._tail[:-1]] + [self._emb.cout], self._conv2.cout
+        L = len(widths)
+        entry, stem, _ = _CHAINS[self.precision]["embed"]
+        if self._emb.kin != widths[-2] or not getattr(dll(), stem + "_supported")(K0, L, (ctypes.c_int32 * L)(*widths), parts):
+            raise NotImplementedError("FrozenPartSeg.embed(): a tail of %d input columns, widths %s and %d parts is outside "
+                                      "%s (4 layers of 128, at most 64 parts, at most 160 columns); there is no "
+                                      "fall-back" % (K0, tuple(widths), parts, entry))
+        return K0, widths, parts
+
+    def embed(self, xyz, cls_label, fps_start=None, l2_norm=None, shape_cat=None, cat_of_label=None, return_labels=False):
+        """The per-point embedding the primitive fitting consumes: xyz [B, C, N], cls_label as forward() -> emb [B, N, 128]
+        fp32, row-major and contiguous (the layout fit_ops.cluster / convex_loss work on), extra_conv_emb(relu(bn1(conv1(
+        fp1(...))))); l2_norm=True divides every point's 128 channels by max(their 2-norm, 1e-12) (F.normalize), None takes the
+        live model's `l2_norm`.  return_labels=True: (emb, labels [B, N] int32) from the SAME launch, labels as labels()
+        gives them for (shape_cat, cat_of_label) -- both or neither.
+        labels()'s route up to fp1's rows, then ONE launch (_chain_embed) over fp1's two layers, conv1 + bn1 and the two
+        heads: no [B N, 128] tensor but the embedding itself.  No fall-back: NotImplementedError for a tail the kernel
+        refuses."""
+        if (shape_cat is None) != (cat_of_label is None):
+            raise ValueError("FrozenPartSeg.embed(): shape_cat and cat_of_label go together (both or neither)")
+        if shape_cat is not None and not return_labels:
+            raise ValueError("FrozenPartSeg.embed(): shape_cat and cat_of_label restrict the labels: pass return_labels=True")
+        if xyz.dim() != 3:
+            raise ValueError("FrozenPartSeg.embed(): xyz must be [B, C, N], got %s" % (tuple(xyz.shape),))
+        B, _, N = xyz.shape
+        K0, widths, parts = self._embed_shape()
+        if l2_norm is None:
+            l2_norm = bool(getattr(self._source, "l2_norm", False))
+        if shape_cat is not None:
+            shape_cat, cat_of_label = torch.as_tensor(shape_cat), torch.as_tensor(cat_of_label)
+            for name, t, n in (("shape_cat", shape_cat, B), ("cat_of_label", cat_of_label, parts)):
+                if t.dtype.is_floating_point or t.dtype == torch.bool or t.numel() != n:
+                    raise ValueError("FrozenPartSeg.embed(): %s must hold %d integers, got %s %s"
+                                     % (name, n, t.dtype, tuple(t.shape)))
+        with torch.no_grad():
+            pts, l0_xyz, l1_xyz, skip, l1_up, _, _ = self._trunk(xyz, cls_label, fps_start)
+            dev = pts.device
+            if shape_cat is not None:
+                shape_cat = shape_cat.reshape(B).to(device=dev, dtype=torch.int32).contiguous()
+                cat_of_label = cat_of_label.reshape(parts).to(device=dev, dtype=torch.int32).contiguous()
+            rows = self._fp_rows("fp1", l0_xyz, l1_xyz, skip, l1_up, K0)
+            emb = torch.empty(B, N, widths[-1], dtype=torch.float32, device=dev)
+            out = torch.empty(B, N, dtype=torch.int32, device=dev) if return_labels else None
+            self._chain_embed(rows, K0, widths, parts, emb, bool(l2_norm), out, cat_of_label, shape_cat, N)
+        return (emb, out) if return_labels else emb
 
     def probe_step(self, xyz, cls_label, target, fps_start=None):
         """One iteration of the classifier-layer pre-training (train_partseg_shapenet.py:56-99, `--init_cls`):
@@ -558,6 +616,26 @@ class FrozenPartSeg(nn.Module):
             call(entry, ptr(rows), _LL(K0), _LL(P), K0, L, (ctypes.c_int32 * L)(*widths), nn_ops._ptr_array(list(Ws)),
                  (ctypes.c_longlong * L)(*lds), nn_ops._ptr_array([ly.b for ly in self._tail]), ptr(scores), _LL(widths[-1]),
                  ptr(labels), ptr(cat_of_label), ptr(shape_cat), N, ptr(ws), cur_stream())
+
+    def _chain_embed(self, rows, K0, widths, parts, emb, normalize, labels, cat_of_label, shape_cat, N):
+        """fp1's rows [P, K0] -> emb [.., 128] (unit rows with `normalize`) and, with `labels`, conv2's restricted arg-max, in
+        one launch: layers 1 .. 3 of the tail, then extra_conv_emb and (labels only) conv2 on the same registers."""
+        chain = _CHAINS[self.precision]
+        entry, stem, tag = chain["embed"]
+        P, L = rows.shape[0], len(widths)
+        layers = [self._tail_w0] + self._tail[1:-1] + [self._emb, self._conv2]
+        bf16 = self._tail_bf16[:-1] + self._emb_bf16 + self._tail_bf16[-1:] if self._bf16 else [None] * (L + 1)
+        Ws, lds = zip(*(chain["weight"](ly, w) for ly, w in zip(layers, bf16)))
+        CL = parts if labels is not None else 0
+        cw = (ctypes.c_int32 * L)(*widths)
+        nws = getattr(dll(), stem + "_workspace")(P, K0, L, cw, CL)
+        ws = torch.empty(nws, dtype=torch.float32, device=rows.device) if nws else None
+        flops = 2.0 * P * (sum(k * c for k, c in zip([K0] + widths[:-1], widths)) + widths[-2] * CL)
+        with profiler.span(profiler.tag(tag, P, K0, *widths, CL), flops):
+            call(entry, ptr(rows), _LL(K0), _LL(P), K0, L, cw, nn_ops._ptr_array(list(Ws[:L])), (ctypes.c_longlong * L)(*lds[:L]),
+                 nn_ops._ptr_array([ly.b for ly in self._tail[:-1]] + [self._emb.b]), ptr(Ws[L]) if CL else None, _LL(lds[L]),
+                 ptr(self._conv2.b) if CL else None, CL, ptr(emb), _LL(emb.stride(-2)), int(normalize), None, _LL(0), ptr(labels),
+                 ptr(cat_of_label), ptr(shape_cat), N, ptr(ws), cur_stream())
 
     def _fp_level(self, name, xyz1, xyz2, points1, points2):
         """Feature propagation: xyz1 [B,N,3], xyz2 [B,S,3] (None: S == 1), points1 [B,N,D1], points2 [B,S,D2] -> [B,N,C]."""
